@@ -1,8 +1,17 @@
 """Benchmark of the north-star hot path: one average_distortion forward+backward per step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1 without a launcher: bench.py starts its own N ranks, one per GPU over RCCL, and rank 0 prints the
      line; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it just joins)
+
+A plain run sets up, warms up (W steps, then an untimed spin-up until the clocks have settled), times exactly K
+steps once and prints the line: metric/value = edges/s/iter over those K steps, ms_per_step = their mean.
+--dump-outputs DIR writes what the last timed step computed -- DIR/grad.npy ([n, d] float32) and DIR/loss.npy
+(float32) -- from inputs that are the same on every run with the same arguments.
+--full adds everything else, as the default run did before it existed: the timed region repeated (--blocks,
+default 11; `ms_per_step` / `value` are then the MEDIAN block), the per-step HIP-event median, the roofline and the
+per-rank kernel times below, the fp32 and byte-index parameter streams, the CPU baselines and, with
+--survey-seed, the oracle's loss.
 
 Default workload = BASELINE.json configs[3] ("Synthetic scale"): n = 1M items,
 |E| = 50M uniform-random edges (out-degree 50), d = 2, penalties.Log1p(exponent 1.5), weights in
@@ -10,7 +19,7 @@ Default workload = BASELINE.json configs[3] ("Synthetic scale", SURVEY 8d config
 scalar loss and the full [n, d] gradient on every rank (multi-GPU: incl. the exchange of
 [grad | loss]).  The problem size is fixed as N grows (strong scaling, as the metric is stated).
 
-Prints ONE JSON line: metric/value = edges/s/iter, plus
+Prints ONE JSON line: metric/value = edges/s/iter, plus (--full)
   roofline     -- algorithmic bytes (12.32 B/edge) / fused-kernel duration (median of
                   per-launch HIP-event times on the launching stream), against the 8 TB/s HBM peak;
                   `traffic` = HBM bytes per launch from the rocprofv3 PMC passes of THIS kernel
@@ -19,7 +28,6 @@ Prints ONE JSON line: metric/value = edges/s/iter, plus
                   pow/sum/sqrt, the penalty under autograd, two scatter_add_) restated in torch and
                   timed on ALL of this host's cores (kind "torch-aten-sequence"); the OpenMP CPU
                   oracle (a port of the algorithm) beside it as `port`  (N = 1 only)
-The timed region is repeated (--blocks, default 10); `ms_per_step` / `value` are the MEDIAN block.
 
 Other workloads (secondary records; same JSON shape):
   --variant 4b SURVEY 8d config 4b: the last third of the edges repulsive, PushAndPull(Log1p, Log)
@@ -332,6 +340,25 @@ def time_launches(fn, count, device, spin=True):
     return float(np.median(t)), float(t.mean())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, grad, loss):
+    """--dump-outputs: the last timed step's gradient and loss as path/grad.npy ([n, d] float32) and path/loss.npy
+    (float32, shape [1]).  A gradient above the 64 MB budget is cut to a fixed, seeded sample of its rows, whose
+    indices go to path/grad_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    g = grad.detach().float().cpu().numpy()
+    n, d = g.shape
+    rows_max = (DUMP_LIMIT_BYTES - (1 << 16)) // (4 * d + 8)
+    if n > rows_max:
+        rows = np.sort(np.random.default_rng(0).choice(n, rows_max, replace=False))
+        np.save(os.path.join(path, "grad_rows.npy"), rows.astype(np.float64))
+        g = g[rows]
+    np.save(os.path.join(path, "grad.npy"), np.ascontiguousarray(g, dtype=np.float32))
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+
+
 # ------------------------------------------------------------------------------------------ config 4
 def timed_blocks(step, barrier, steps, blocks, world, device):
     """`blocks` repetitions of the timed region (barrier + sync, `steps` steps, barrier + sync);
@@ -429,11 +456,54 @@ def run_config4(args, world, rank, device):
     # spin-up (untimed, beside the caller's warm-up steps): until the step time has settled -- the blocks below are
     # then steady state whatever --steps is
     spinup = spin_up(step, device, label="headline blocks") if world == 1 else 0
-    # the timed region (exactly `steps` steps between barrier + synchronize), repeated: the median
-    # block is reported (a 5 ms region is at the mercy of one scheduler hiccup)
+    # the timed region (exactly `steps` steps between barrier + synchronize); --full repeats it and reports the
+    # median block (a 5 ms region is at the mercy of one scheduler hiccup)
     block_s = timed_blocks(step, barrier, args.steps, max(args.blocks, 1), world, device)
     elapsed = float(np.median(block_s))
-    # the same steps once more with a HIP-event pair around each one: the per-step median (the
+    gpu_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, grad, loss)
+    layout = int(binding.struct(d).layout)
+    ring = plan.ring_info()
+
+    out = {
+        "metric": "edges/sec/iter (avg_distortion fwd+bwd), n=1M |E|=50M d=2" if headline_shape else
+                  "edges/sec/iter (avg_distortion fwd+bwd), n=%d |E|=%d d=%d, %s graph" % (n, p, d, args.graph),
+        "value": p * args.steps / elapsed, "unit": "edges/s/iter",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_launches": spinup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "blocks": len(block_s), "ms_per_step_blocks": [round(1e3 * b / args.steps, 5) for b in block_s],
+        "ms_per_step_fastest_block": 1e3 * min(block_s) / args.steps,
+        "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[3] / SURVEY 8d config %s%s: n=%d, |E|=%d %s edges "
+                               "(out-degree %d), d=%d, %s; %s" % (args.variant, "" if headline_shape else " at ANOTHER SHAPE (secondary record)",
+                                                                   n, p, {"uniform": "uniform-random", "hub": "uniform-random + one hub of degree 5e5",
+                                                                          "powerlaw": "preferential-attachment (copy model)",
+                                                                          "clusters": "planted-cluster"}[args.graph], args.degree, d, fname,
+                               "the survey's exact tensors: numpy default_rng(0) edges and weights, torch.manual_seed(0) "
+                               "CPU randn X, built on the host and uploaded (--survey-seed)" if args.survey_seed else
+                               "seeded on the device with torch.Generator(0) (the survey's recipe uses numpy "
+                               "default_rng(0): same distribution, another stream; --survey-seed builds that one)"),
+                   "parallelism": ("vertex-range shards x%d + %s of [grad|loss]" % (world, exchange.mode))
+                   if world > 1 else ("single GPU" if args.emulate_world <= 1 else
+                                      "rank 0 of a %d-way shard, kernel only (emulation, no collective)" % args.emulate_world),
+                   "exchange": exchange.mode if world > 1 else None,
+                   "parameter_stream": ("codebook: %d distinct weights ride in the packed half-edge word "
+                                        "(4 B/half-edge)" % (2 if args.variant == "4a" else 3) if binding.codebook
+                                        else "byte index: one index byte per half-edge beside the packed word (5 B/half-edge)"
+                                        if binding.byte_stream else "fp32 weight per half-edge (8 B/half-edge)"),
+                   "ring_layout": ring if layout == 1 else None,
+                   "ms_per_1e8_half_edges": 1e3 * elapsed / args.steps * 1e8 / max(plan.half_edges, 1),
+                   "loss": gpu_loss},
+    }
+    if not args.full:
+        if rank != 0:
+            return None
+        out["spinup"] = SPINUP_LOG
+        return out
+
+    # --full: the same steps once more with a HIP-event pair around each one: the per-step median (the
     # events themselves cost a few microseconds per step, so they stay out of the timed region)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     for a, b in ev:
@@ -442,7 +512,6 @@ def run_config4(args, world, rank, device):
         b.record()
     barrier()
     step_ms = np.array([a.elapsed_time(b) for a, b in ev])
-    gpu_loss = float(loss.item())
 
     # dominant kernel: the fused gather/scatter kernel, timed per launch with HIP events on the
     # stream it is launched on (torch's current stream)
@@ -456,9 +525,7 @@ def run_config4(args, world, rank, device):
     edges_local = plan.half_edges / 2.0
     alg_bytes = ALG_BYTES_PER_EDGE * edges_local + 2.0 * 4.0 * d * (plan.row_hi - plan.row_lo)
     achieved = alg_bytes / (k_ms * 1e-3)
-    layout = int(binding.struct(d).layout)
     fn_name = ("Log1p" if args.function == "log1p" else args.function) if args.variant == "4a" else "PushPull<Log1p,Log>"
-    ring = plan.ring_info()
     kernel = ("k_fused_ring<%d,%s,%s> (LDS-resident rows, chunk ring filled through the producers' VGPRs; loss and, with two "
               "column groups per row block, the groups' rows added in the same launch; k_ring_combine behind it otherwise)"
               % (d, fn_name, binding.stream_kind + " stream")) if layout == 1 \
@@ -480,42 +547,12 @@ def run_config4(args, world, rank, device):
 
     if rank != 0:
         return None
-    out = {
-        "metric": "edges/sec/iter (avg_distortion fwd+bwd), n=1M |E|=50M d=2" if headline_shape else
-                  "edges/sec/iter (avg_distortion fwd+bwd), n=%d |E|=%d d=%d, %s graph" % (n, p, d, args.graph),
-        "value": p * args.steps / elapsed, "unit": "edges/s/iter",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_launches": spinup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "ms_per_step_median_events": float(np.median(step_ms)),
-        "blocks": len(block_s), "ms_per_step_blocks": [round(1e3 * b / args.steps, 5) for b in block_s],
-        "ms_per_step_fastest_block": 1e3 * min(block_s) / args.steps,
-        "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[3] / SURVEY 8d config %s%s: n=%d, |E|=%d %s edges "
-                               "(out-degree %d), d=%d, %s; %s" % (args.variant, "" if headline_shape else " at ANOTHER SHAPE (secondary record)",
-                                                                   n, p, {"uniform": "uniform-random", "hub": "uniform-random + one hub of degree 5e5",
-                                                                          "powerlaw": "preferential-attachment (copy model)",
-                                                                          "clusters": "planted-cluster"}[args.graph], args.degree, d, fname,
-                               "the survey's exact tensors: numpy default_rng(0) edges and weights, torch.manual_seed(0) "
-                               "CPU randn X, built on the host and uploaded (--survey-seed)" if args.survey_seed else
-                               "seeded on the device with torch.Generator(0) (the survey's recipe uses numpy "
-                               "default_rng(0): same distribution, another stream; --survey-seed builds that one)"),
-                   "parallelism": ("vertex-range shards x%d + %s of [grad|loss]" % (world, exchange.mode))
-                   if world > 1 else ("single GPU" if args.emulate_world <= 1 else
-                                      "rank 0 of a %d-way shard, kernel only (emulation, no collective)" % args.emulate_world),
-                   "exchange": exchange.mode if world > 1 else None,
-                   "kernel_ms_per_rank": per_rank_ms,
-                   "parameter_stream": ("codebook: %d distinct weights ride in the packed half-edge word "
-                                        "(4 B/half-edge)" % (2 if args.variant == "4a" else 3) if binding.codebook
-                                        else "byte index: one index byte per half-edge beside the packed word (5 B/half-edge)"
-                                        if binding.byte_stream else "fp32 weight per half-edge (8 B/half-edge)"),
-                   "ring_layout": ring if layout == 1 else None,
-                   "ms_per_1e8_half_edges": 1e3 * elapsed / args.steps * 1e8 / max(plan.half_edges, 1),
-                   "loss": gpu_loss},
-        "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK_BPS / 1e9,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_BPS, "traffic": traffic,
-                     "traffic_source": traffic_src, "kernel": kernel, "kernel_ms": k_ms,
-                     "kernel_ms_mean": k_mean, "alg_bytes_per_launch": alg_bytes},
-    }
+    out["ms_per_step_median_events"] = float(np.median(step_ms))
+    out["config"]["kernel_ms_per_rank"] = per_rank_ms
+    out["roofline"] = {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK_BPS / 1e9,
+                       "unit": "GB/s", "frac": achieved / HBM_PEAK_BPS, "traffic": traffic,
+                       "traffic_source": traffic_src, "kernel": kernel, "kernel_ms": k_ms,
+                       "kernel_ms_mean": k_mean, "alg_bytes_per_launch": alg_bytes}
     if world == 1 and binding.codebook and not args.no_codebook and args.variant == "4a" and args.function == "log1p" and headline_shape:
         # secondary: the general case (continuous per-edge parameters, configs 2 / 3) streams an
         # fp32 parameter per half-edge
@@ -1025,7 +1062,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--blocks", type=int, default=11, help="repetitions of the timed region (the median is reported; odd: the median is a measured block)")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="repetitions of the timed region (the median is reported; odd: the median is a measured block); "
+                         "default 11; 1 for a config-4 run without --full")
+    ap.add_argument("--full", action="store_true",
+                    help="config 4: everything beyond the headline figure -- repeated timed blocks, per-step and per-kernel "
+                         "HIP-event times, roofline, other parameter streams, CPU baselines, the oracle check of --survey-seed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 4: write the last timed step's gradient and loss to DIR/grad.npy and DIR/loss.npy")
     ap.add_argument("--config", type=int, default=4, choices=(2, 3, 4, 5))
     ap.add_argument("--variant", default="4a", choices=("4a", "4b"),
                     help="config 4 only: 4a Log1p (the headline), 4b PushAndPull(Log1p, Log) with 1/3 repulsive edges")
@@ -1038,7 +1082,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--survey-seed", action="store_true",
                     help="config 4: SURVEY 8d's exact numpy default_rng(0) / torch.manual_seed(0) workload, built on the "
-                         "host and uploaded; prints its loss next to the oracle's (the default line keeps the device generator)")
+                         "host and uploaded; with --full its loss is printed next to the oracle's (the default line keeps the device generator)")
     ap.add_argument("--no-codebook", action="store_true",
                     help="stream the weights as fp32 (8 B/half-edge) even though they take 2 values")
     ap.add_argument("--n", type=int, default=N_ITEMS)
@@ -1054,6 +1098,10 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="single process: time only the kernel of rank 0 of a W-way shard (no collective)")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 1 if args.config == 4 and not args.full else 11
+    if args.dump_outputs and (args.config != 4 or args.embed or args.exchange_only):
+        raise SystemExit("--dump-outputs writes the outputs of the config-4 evaluation (no --config 2/3/5, --embed, --exchange-only)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))

@@ -201,3 +201,23 @@ def test_sliced_in_place_all_gather_two_gloo_ranks():
         p.join(180)
         assert p.exitcode == 0
     assert ret[0] == 1 and ret[1] == 1
+
+
+def test_bench_dump_outputs_keeps_to_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 gradient and loss; a gradient above the byte budget becomes a fixed, seeded
+    sample of its rows (the same rows on every run), their indices beside it."""
+    import bench
+    g = torch.arange(5000 * 2, dtype=torch.float32).view(5000, 2)
+    loss = torch.tensor([1.5])
+    bench.dump_outputs(str(tmp_path / "whole"), g, loss)
+    assert np.array_equal(np.load(tmp_path / "whole" / "grad.npy"), g.numpy())
+    assert not (tmp_path / "whole" / "grad_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (1 << 16) + 16 * 1000)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), g, loss)
+    rows = np.load(tmp_path / "a" / "grad_rows.npy")
+    got = np.load(tmp_path / "a" / "grad.npy")
+    assert rows.dtype == np.float64 and len(rows) == 1000 and np.all(np.diff(rows) > 0)
+    assert got.dtype == np.float32 and np.array_equal(got, g.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "grad_rows.npy"))
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float32

@@ -621,3 +621,29 @@ def test_ring_layout_fuzz_against_the_csr_kernels():
     out = subprocess.run([sys.executable, os.path.join(root, "tools", "r6_ring_fuzz.py"), "24", "7"], env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "ok, worst" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """`bench.py --steps K` without --full: one timed region of exactly K steps, the headline fields only, and
+    --dump-outputs writes the last step's gradient and loss -- equal to the oracle's on the same seeded inputs."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 20000
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--n", str(n), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["blocks"] == 1 and len(rec["ms_per_step_blocks"]) == 1
+    assert rec["ms_per_step"] > 0 and rec["unit"] == "edges/s/iter" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and "roofline" not in rec and "cpu_baseline" not in rec
+    grad, loss = np.load(tmp_path / "grad.npy"), np.load(tmp_path / "loss.npy")
+    assert grad.dtype == np.float32 and grad.shape == (n, 2) and loss.dtype == np.float32 and loss.shape == (1,)
+    edges, w, X = bench.make_workload(torch.device(DEV, 0), n=n)
+    wE, wgrad = oracle.average_distortion(edges.cpu().numpy(), X.cpu().numpy(), oracle.func("LOG1P", w.cpu().numpy(), None, (1.5,)))
+    assert float(loss[0]) == pytest.approx(wE, rel=1e-5)
+    assert_grad_close(grad, wgrad)

@@ -7,8 +7,8 @@ cd $R
 bash tools/pmc_traffic.sh > $O/pmc_run.log 2>&1
 cp gpurun_out/pmc/pmc_traffic.json gpurun_out/pmc/kernel_stats.csv $O/ 2>/dev/null
 cp $R/gpurun_out/pmc/pmc_traffic.json $R/profiles/r04_pmc_traffic.json 2>/dev/null   # (the bench lines below pick it up)
-python bench.py 2>/dev/null | tail -1 > $O/bench_line.json
-python bench.py --no-cpu-baseline --variant 4b 2>/dev/null | tail -1 > $O/config4b_bench_line.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_line.json
+python bench.py --full --no-cpu-baseline --variant 4b 2>/dev/null | tail -1 > $O/config4b_bench_line.json
 python bench.py --config 4 --embed 2>/dev/null | tail -1 > $O/config4_embed_bench_line.json
 bash tools/prof_cmd.sh c4embed python $R/bench.py --config 4 --embed > $O/config4_embed_kernels.txt 2>&1
 cp gpurun_out/c4embed_kernel_stats.csv $O/config4_embed_kernel_stats.csv 2>/dev/null
@@ -16,5 +16,5 @@ python bench.py --config 2 2>/dev/null | tail -1 > $O/config2_bench_line.json
 python bench.py --config 3 2>/dev/null | tail -1 > $O/config3_bench_line.json
 python bench.py --config 5 2>/dev/null | tail -1 > $O/config5_bench_line.json
 python bench.py --config 5 --embed 2>/dev/null | tail -1 > $O/config5_embed_bench_line.json
-for W in 2 4 8; do python bench.py --no-cpu-baseline --emulate-world $W --steps 50 --blocks 5 2>/dev/null | tail -1 > $O/shard_W$W.json; done
+for W in 2 4 8; do python bench.py --full --no-cpu-baseline --emulate-world $W --steps 50 --blocks 5 2>/dev/null | tail -1 > $O/shard_W$W.json; done
 ls -la $O

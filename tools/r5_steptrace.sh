@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/steptrace
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $OUT/p --output-format csv -- python $R/bench.py --steps 50 --blocks 3 --no-cpu-baseline > $OUT/line.json 2> $OUT/err.txt
+rocprofv3 --kernel-trace -d $OUT/p --output-format csv -- python $R/bench.py --full --steps 50 --blocks 3 --no-cpu-baseline > $OUT/line.json 2> $OUT/err.txt
 cd $R
 python - <<'PY'
 import csv, glob, statistics

@@ -17,23 +17,23 @@ pmc _4b --variant 4b
 pmc _d3 --dim 3
 pmc _n2m --n 2000000
 pmc _c5 --config 5
-python bench.py 2>/dev/null | tail -1 > $O/bench_line.json
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_line_driver_command.json
-python bench.py --no-cpu-baseline --survey-seed 2>/dev/null | tail -1 > $O/survey_seed_bench_line.json
-python bench.py --no-cpu-baseline --variant 4b 2>/dev/null | tail -1 > $O/config4b_bench_line.json
-python bench.py --no-cpu-baseline --dim 3 2>/dev/null | tail -1 > $O/d3_bench_line.json
-python bench.py --no-cpu-baseline --n 2000000 2>/dev/null | tail -1 > $O/n2m_bench_line.json
-python bench.py --no-cpu-baseline --n 4000000 --steps 50 2>/dev/null | tail -1 > $O/n4m_bench_line.json
-python bench.py --no-cpu-baseline --graph hub 2>/dev/null | tail -1 > $O/hub_bench_line.json
-python bench.py --no-cpu-baseline --graph powerlaw 2>/dev/null | tail -1 > $O/powerlaw_bench_line.json
-python bench.py --no-cpu-baseline --graph powerlaw --dim 3 2>/dev/null | tail -1 > $O/powerlaw_d3_bench_line.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_line.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_line_driver_command.json
+python bench.py --full --no-cpu-baseline --survey-seed 2>/dev/null | tail -1 > $O/survey_seed_bench_line.json
+python bench.py --full --no-cpu-baseline --variant 4b 2>/dev/null | tail -1 > $O/config4b_bench_line.json
+python bench.py --full --no-cpu-baseline --dim 3 2>/dev/null | tail -1 > $O/d3_bench_line.json
+python bench.py --full --no-cpu-baseline --n 2000000 2>/dev/null | tail -1 > $O/n2m_bench_line.json
+python bench.py --full --no-cpu-baseline --n 4000000 --steps 50 2>/dev/null | tail -1 > $O/n4m_bench_line.json
+python bench.py --full --no-cpu-baseline --graph hub 2>/dev/null | tail -1 > $O/hub_bench_line.json
+python bench.py --full --no-cpu-baseline --graph powerlaw 2>/dev/null | tail -1 > $O/powerlaw_bench_line.json
+python bench.py --full --no-cpu-baseline --graph powerlaw --dim 3 2>/dev/null | tail -1 > $O/powerlaw_d3_bench_line.json
 python bench.py --config 4 --embed 2>/dev/null | tail -1 > $O/config4_embed_bench_line.json
 python bench.py --config 4 --embed --graph clusters 2>/dev/null | tail -1 > $O/config4_embed_clusters_bench_line.json
 python bench.py --config 2 2>/dev/null | tail -1 > $O/config2_bench_line.json
 python bench.py --config 3 2>/dev/null | tail -1 > $O/config3_bench_line.json
 python bench.py --config 5 2>/dev/null | tail -1 > $O/config5_bench_line.json
 for W in 2 4 8; do
-  python bench.py --no-cpu-baseline --emulate-world $W --steps 50 --blocks 5 2>/dev/null | tail -1 > $O/shard_W$W.json
+  python bench.py --full --no-cpu-baseline --emulate-world $W --steps 50 --blocks 5 2>/dev/null | tail -1 > $O/shard_W$W.json
   python bench.py --config 4 --embed --emulate-world $W --steps 30 2>/dev/null | tail -1 > $O/config4_embed_shard_W$W.json
 done
 ls -la $O

@@ -8,8 +8,8 @@ OUT=$R/gpurun_out/shard
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for W in 2 4 8; do
-  python $R/bench.py --emulate-world $W --steps 200 --no-cpu-baseline 2> $OUT/W$W.err | tail -1 > $OUT/W${W}_bench_line.json
-  rocprofv3 --kernel-trace --stats -d $OUT/prof$W --output-format csv -- python $R/bench.py --emulate-world $W --steps 100 --no-cpu-baseline > /dev/null 2> $OUT/prof$W.err
+  python $R/bench.py --full --emulate-world $W --steps 200 --no-cpu-baseline 2> $OUT/W$W.err | tail -1 > $OUT/W${W}_bench_line.json
+  rocprofv3 --kernel-trace --stats -d $OUT/prof$W --output-format csv -- python $R/bench.py --full --emulate-world $W --steps 100 --no-cpu-baseline > /dev/null 2> $OUT/prof$W.err
   f=$(find $OUT/prof$W -name "*kernel_stats.csv" | head -1)
   # the ring and combine kernels only (the rest is problem generation and the plan build)
   (head -1 $f; grep -E "k_fused_ring|k_ring_combine" $f) > $OUT/W${W}_kernel_stats.csv
