@@ -257,6 +257,26 @@ int mde_edges_count_unique(int64_t n, int64_t p, const int64_t* edges, int64_t* 
  * sqn_work: n floats of scratch.  The Gram tiles run on the f32 matrix cores. */
 int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_out, float* d2_out,
             float* sqn_work, void* stream);
+/* Sparse data matrices (SURVEY 8f rows f2 / f4 on scipy.sparse inputs) [ref: preprocess/data_matrix.py:11-178].
+ * Every entry below takes one device CSR of n rows and nf columns: indptr int64 [n + 1], indices int32
+ * [nnz] (column ids, strictly increasing within a row), values float32 [nnz]; n < 2^31, nf < 2^31, nnz may
+ * exceed 2^31, rows may be empty.  Each validates the CSR on the device first (reads stay inside the
+ * arrays) and returns MDE_E_INVALID with a message when indptr[0] != 0, indptr decreases, indptr[n] != nnz,
+ * a column id lies outside [0, nf) or a row's ids are not strictly increasing.  SYNC (the validation). */
+int mde_sparse_validate(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                        const float* values, void* stream);
+/* Exact k nearest neighbours (Euclidean) of every row of the CSR, same contract as mde_knn: idx_out [n, k]
+ * int32 (self excluded by index; -1 when fewer than k other rows exist), d2_out [n, k] squared distances
+ * ascending per row, ties to the smaller index; 1 <= k <= 64; sqn_work: n floats of scratch (row squared
+ * norms).  Bit-reproducible from run to run.  SYNC (the validation; the search itself is enqueued). */
+int mde_sparse_knn(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                   const float* values, int32_t k, int32_t* idx_out, float* d2_out, float* sqn_work,
+                   void* stream);
+/* out[e] = ||x_i - x_j|| for every edge (i, j) of edges [p, 2] (int64), summed over the union of the two
+ * rows' columns as (a - b)^2 in double -- no cancellation, near-duplicate rows come out near zero.  An
+ * endpoint outside [0, n) gives NaN.  Reproducible from run to run.  SYNC (the validation). */
+int mde_sparse_distances(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                         const float* values, int64_t p, const int64_t* edges, float* out, void* stream);
 /* Shortest-path distances on the graph whose edges built `plan` (a FULL plan; its symmetrised CSR
  * is the adjacency) [ref: preprocess/graph.py:286-474, _graph.pyx:10-52].
  * w: per-half-edge edge lengths in plan (CSR) order (mde_plan_expand), or NULL for unit lengths

@@ -9,6 +9,7 @@
 // 64 candidates into the row's sorted top-k list (insertion only when a candidate beats the current
 // k-th best, which becomes rare quickly).  Self matches are excluded by index.
 #include "mde_common.h"
+#include "mde_topk.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -106,24 +107,8 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn(int n, int nf, int k, const f
       sD[r * (KNN_BN + 1) + c] = d2;
     }
     __syncthreads();
-    if (tid < KNN_BM) {
-      float* bd = bestd + tid * k;
-      int* bi = besti + tid * k;
-      for (int c = 0; c < KNN_BN; ++c) {
-        const float d2 = sD[tid * (KNN_BN + 1) + c];
-        if (d2 < worst) {
-          int pos = k - 1;
-          while (pos > 0 && bd[pos - 1] > d2) {
-            bd[pos] = bd[pos - 1];
-            bi[pos] = bi[pos - 1];
-            --pos;
-          }
-          bd[pos] = d2;
-          bi[pos] = col0 + c;
-          worst = bd[k - 1];
-        }
-      }
-    }
+    if (tid < KNN_BM)
+      mde_topk_merge(sD + tid * (KNN_BN + 1), KNN_BN, col0, k, bestd + tid * k, besti + tid * k, worst);
   }
   __syncthreads();
   for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {

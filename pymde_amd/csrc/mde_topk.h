@@ -1,0 +1,27 @@
+// mde_topk.h -- the per-row top-k merge shared by the dense (mde_knn.hip) and sparse (mde_sparse.hip)
+// exact k-NN kernels.
+#pragma once
+#include "mde_common.h"
+
+// One thread merges a parked tile row of `ncand` squared distances (candidate c has index c0 + c) into
+// its row's sorted top-k list (bd ascending, bi the indices).  `worst` is the current k-th best and is
+// kept in a register by the caller between tiles.  A candidate enters only when strictly below the
+// k-th best and is inserted behind every equal distance: with candidates offered in increasing index
+// order, ties resolve to the smaller index (the order of a stable argsort).
+__device__ __forceinline__ void mde_topk_merge(const float* __restrict__ sd, int ncand, int c0, int k,
+                                               float* __restrict__ bd, int* __restrict__ bi, float& worst) {
+  for (int c = 0; c < ncand; ++c) {
+    const float d2 = sd[c];
+    if (d2 < worst) {
+      int pos = k - 1;
+      while (pos > 0 && bd[pos - 1] > d2) {
+        bd[pos] = bd[pos - 1];
+        bi[pos] = bi[pos - 1];
+        --pos;
+      }
+      bd[pos] = d2;
+      bi[pos] = c0 + c;
+      worst = bd[k - 1];
+    }
+  }
+}

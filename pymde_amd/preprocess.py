@@ -14,6 +14,7 @@ import ctypes
 import torch
 
 from pymde_amd import _lib
+from pymde_amd import sparse as _sparse
 from pymde_amd import util
 
 
@@ -107,23 +108,51 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     Neighbours farther than ``max_distance`` do not count (an edge whose both directions are too
     long disappears).  The reference is exact (sklearn brute force) below 10 000 items and
     approximate (pynndescent) above; this search is exact at every size.  Self matches are
-    excluded by index, so duplicated rows become ordinary zero-distance neighbours."""
+    excluded by index, so duplicated rows become ordinary zero-distance neighbours.
+
+    ``data`` is a dense ``np.ndarray`` / ``torch.Tensor`` [n, n_features], a sparse data matrix (a
+    scipy sparse matrix of any format, or a torch sparse COO / CSR tensor; searched by the sparse
+    kernel, or densified into the dense one where that is faster, ``_densify_sparse_knn``), or a
+    ``Graph``."""
     if hasattr(data, "edges") and hasattr(data, "n_items") and not isinstance(data, torch.Tensor):
         from pymde_amd import graph as _graph
         return _graph.k_nearest_neighbors(data, k, graph_distances=graph_distances,
                                           max_distance=max_distance)
+    if _sparse.is_sparse(data):
+        csr = _sparse.to_device_csr(data, device)
+        k = _clamp_k(k, csr.n)
+        if _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
+            idx, d2 = _dense_knn_lists(csr.to_dense(), k)
+        else:
+            idx, d2 = _sparse_knn_lists(csr, k)
+        max_d2 = None if max_distance is None else float(max_distance) ** 2
+        return _neighbor_lists_to_graph(csr.n, k, idx, d2, max_d2, csr.device)
     if not isinstance(data, torch.Tensor):
         data = torch.as_tensor(data)
     if device is None:
         device = data.device if data.is_cuda else util.get_default_device()
     device = util.require_cuda_device(device)
     data = data.to(device=device, dtype=torch.float32).contiguous()
-    n, nf = int(data.shape[0]), int(data.shape[1])
+    n = int(data.shape[0])
+    k = _clamp_k(k, n)
+    idx, d2 = _dense_knn_lists(data, k)
+    max_d2 = None if max_distance is None else float(max_distance) ** 2
+    return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
+
+
+def _clamp_k(k, n):
     k = int(k)
     if k > n - 1:
         k = n - 1
     if k < 1:
         raise ValueError("k must be at least 1")
+    return k
+
+
+def _dense_knn_lists(data, k):
+    """Directed neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the GPU."""
+    n, nf = int(data.shape[0]), int(data.shape[1])
+    device = data.device
     lib = _lib.load()
     idx = torch.empty((n, k), dtype=torch.int32, device=device)
     d2 = torch.empty((n, k), dtype=torch.float32, device=device)
@@ -131,8 +160,40 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     with torch.cuda.device(device):
         _lib.check(lib.mde_knn(n, nf, _lib.ptr(data), k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(sqn),
                                _lib.stream_ptr(device)))
-    max_d2 = None if max_distance is None else float(max_distance) ** 2
-    return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
+    return idx, d2
+
+
+def _sparse_knn_lists(csr, k):
+    """Directed neighbour lists of a ``sparse.DeviceCSR`` by the sparse kernel."""
+    device = csr.device
+    lib = _lib.load()
+    idx = torch.empty((csr.n, k), dtype=torch.int32, device=device)
+    d2 = torch.empty((csr.n, k), dtype=torch.float32, device=device)
+    sqn = torch.empty(csr.n, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.mde_sparse_knn(csr.n, csr.n_features, csr.nnz, _lib.ptr(csr.indptr), _lib.ptr(csr.indices),
+                                      _lib.ptr(csr.values), k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(sqn),
+                                      _lib.stream_ptr(device)))
+    return idx, d2
+
+
+# Sparse k-NN dispatcher.  Both kernels cost ~n^2: the dense one per feature, the sparse one per stored
+# entry plus a fixed price per feature window.  Measured at k = 15 (tools/sparse_knn_scale.py,
+# profiles/r07_sparse_knn.txt): the dense MFMA kernel runs ~73 TFLOP/s, the sparse kernel 0.04-1.5 TFMA/s
+# (per query x stored entry), so densifying wins at every recorded shape whose dense copy fits -- 70k x 784
+# at 17 %: 0.12 s against 0.44 s; 100k x 20k at 4.9 %: 5.4 s against 12.5 s; 400k x 20k at 2 %: 74 s against
+# 143 s; 100k x 100k at 0.1 %: 27.3 s against 27.5 s.  The sparse kernel serves the
+# inputs whose dense copy does not fit in DENSIFY_MAX_FRACTION of the free device memory.
+DENSIFY_DENSITY = 0.0
+DENSIFY_MAX_FRACTION = 0.25   # the dense copy may take at most this share of the free device memory
+
+
+def _densify_sparse_knn(n, nf, nnz, device):
+    """True when the sparse data matrix should be densified into the dense k-NN kernel."""
+    if nnz < DENSIFY_DENSITY * float(n) * float(nf):
+        return False
+    free, _ = torch.cuda.mem_get_info(device)
+    return 4.0 * n * nf <= DENSIFY_MAX_FRACTION * free
 
 
 def _rms(distances):

@@ -18,6 +18,7 @@ from pymde_amd import preprocess
 from pymde_amd import problem
 from pymde_amd import util
 from pymde_amd import quadratic
+from pymde_amd import sparse as _sparse
 from pymde_amd.functions import losses, penalties
 
 
@@ -34,7 +35,21 @@ class EdgeGraph(object):
 def distances(data, retain_fraction=1.0, seed=None, device=None):
     """Euclidean distances between (a sample of) the pairs of rows of a data matrix
     [ref: preprocess/data_matrix.py:11-88].  All ``n (n-1)/2`` pairs when ``retain_fraction >= 1``,
-    otherwise a uniform sample of that fraction."""
+    otherwise a uniform sample of that fraction.
+
+    ``data`` is a dense ``np.ndarray`` / ``torch.Tensor`` or a sparse data matrix (scipy sparse, any
+    format, or a torch sparse COO / CSR tensor); sparse distances are summed over the union of the
+    two rows' columns (``mde_sparse_distances``), so near-duplicate rows come out near zero."""
+    if _sparse.is_sparse(data):
+        csr = _sparse.to_device_csr(data, device)
+        edges = _distance_edges(csr.n, retain_fraction, seed, csr.device)
+        lib = _lib.load()
+        delta = torch.empty(edges.shape[0], dtype=torch.float32, device=csr.device)
+        with torch.cuda.device(csr.device):
+            _lib.check(lib.mde_sparse_distances(csr.n, csr.n_features, csr.nnz, _lib.ptr(csr.indptr),
+                                                _lib.ptr(csr.indices), _lib.ptr(csr.values), edges.shape[0],
+                                                _lib.ptr(edges), _lib.ptr(delta), _lib.stream_ptr(csr.device)))
+        return EdgeGraph(edges, delta, csr.n)
     if not isinstance(data, torch.Tensor):
         data = torch.as_tensor(data)
     if device is None:
@@ -42,20 +57,24 @@ def distances(data, retain_fraction=1.0, seed=None, device=None):
     device = util.require_cuda_device(device)
     data = data.to(device=device, dtype=torch.float32).contiguous()
     n, nf = int(data.shape[0]), int(data.shape[1])
-    all_edges = n * (n - 1) // 2
-    max_distances = int(retain_fraction * all_edges)
-    if max_distances <= 0:
-        raise ValueError("max_distances must be positive")
-    if max_distances >= all_edges:
-        edges = util.all_edges(n).to(device).contiguous()
-    else:
-        edges = preprocess.sample_edges(n, max_distances, seed=seed, device=device)
+    edges = _distance_edges(n, retain_fraction, seed, device)
     lib = _lib.load()
     delta = torch.empty(edges.shape[0], dtype=torch.float32, device=device)
     with torch.cuda.device(device):
         _lib.check(lib.mde_distances(n, edges.shape[0], _lib.ptr(edges), _lib.ptr(data), nf,
                                      _lib.ptr(delta), _lib.stream_ptr(device)))
     return EdgeGraph(edges, delta, n)
+
+
+def _distance_edges(n, retain_fraction, seed, device):
+    """All pairs i < j when ``retain_fraction >= 1``, otherwise a uniform sample of that fraction."""
+    all_edges = n * (n - 1) // 2
+    max_distances = int(retain_fraction * all_edges)
+    if max_distances <= 0:
+        raise ValueError("max_distances must be positive")
+    if max_distances >= all_edges:
+        return util.all_edges(n).to(device).contiguous()
+    return preprocess.sample_edges(n, max_distances, seed=seed, device=device)
 
 
 def _remove_anchor_anchor_edges(edges, data, anchors):
@@ -73,10 +92,12 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     """An MDE problem that preserves the pairwise Euclidean distances of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
-    length.  Call ``.embed()`` on the result."""
+    length.  ``data`` is a dense ``np.ndarray`` / ``torch.Tensor``, a sparse data matrix (scipy
+    sparse or a torch sparse COO / CSR tensor -- a data matrix, not an adjacency matrix), or a
+    ``Graph``.  Call ``.embed()`` on the result."""
     is_graph = isinstance(data, _graph.Graph)
     if not is_graph and not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
-        raise ValueError("`data` must be a np.ndarray/torch.Tensor data matrix, or a pymde_amd.Graph.")
+        raise ValueError("`data` must be a np.ndarray/torch.Tensor/sparse data matrix, or a pymde_amd.Graph.")
     n_items = data.n_items if is_graph else int(data.shape[0])
     n_all_edges = n_items * (n_items - 1) / 2
     retain_fraction = max_distances / n_all_edges
@@ -108,16 +129,18 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     """An MDE problem that preserves the k-nearest-neighbour structure of a data matrix
     (rows = items) [ref: recipes.py:221-448]: k-NN graph (weights 1 / 2), optional spectral
     initialisation, uniformly sampled repulsive edges (weight -1), ``PushAndPull`` of the two
-    penalties.  ``data`` may also be a ``Graph``: neighbourhoods are then taken under its
-    shortest-path metric.  Every stage runs on the GPU (rows f2, f3, a10, f1 of SURVEY section 8)."""
+    penalties.  ``data`` is a dense ``np.ndarray`` / ``torch.Tensor``, a sparse data matrix (scipy
+    sparse or a torch sparse COO / CSR tensor; a data matrix, not an adjacency matrix), or a
+    ``Graph``: neighbourhoods are then taken under its shortest-path metric.  Every stage runs on the
+    GPU (rows f2, f3, a10, f1 of SURVEY section 8)."""
     is_graph = isinstance(data, _graph.Graph)
-    if not is_graph and not isinstance(data, torch.Tensor):
+    if not is_graph and not isinstance(data, torch.Tensor) and not _sparse.is_sparse(data):
         data = torch.as_tensor(data)
     if device is None:
         if is_graph:
             device = data.edges.device
         else:
-            device = data.device if data.is_cuda else util.get_default_device()
+            device = data.device if isinstance(data, torch.Tensor) and data.is_cuda else util.get_default_device()
     device = util.require_cuda_device(device)
     n = int(data.n_items) if is_graph else int(data.shape[0])
     if n_neighbors is None:
@@ -188,7 +211,7 @@ def laplacian_embedding(data, embedding_dim=2, n_neighbors=None, max_distance=No
                         device=None, verbose=False):
     """An MDE problem whose solution is a Laplacian embedding [ref: recipes.py:451-503]: the k-NN
     graph of ``preserve_neighbors`` with quadratic penalties, no repulsion and the standardization
-    constraint."""
+    constraint.  ``data`` as for ``preserve_neighbors`` (dense, sparse or a ``Graph``)."""
     return preserve_neighbors(data, embedding_dim=embedding_dim, attractive_penalty=penalties.Quadratic,
                               repulsive_penalty=None, n_neighbors=n_neighbors, max_distance=max_distance,
                               init=init, device=device, verbose=verbose)
