@@ -257,6 +257,33 @@ int mde_edges_count_unique(int64_t n, int64_t p, const int64_t* edges, int64_t* 
  * sqn_work: n floats of scratch.  The Gram tiles run on the f32 matrix cores. */
 int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_out, float* d2_out,
             float* sqn_work, void* stream);
+/* out[r] = |data[r]|^2 for the rows of data [n, nf] (f32; the norms mde_knn forms internally). */
+int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* out, void* stream);
+/* Approximate k-NN by an inverted file (csrc/mde_ann.hip) [ref: preprocess/data_matrix.py:125-143].
+ * Query-against-base search restricted to block-sparse (query tile, candidate range) pairs.  Query
+ * position p reads row q_map[p] of Q [n_q, nf] (q_map NULL: row p), base position c reads row b_map[c] of
+ * B [n_b, nf]; q_sqn / b_sqn are the row norms (mde_row_sqnorm).  List l is the base positions
+ * [offsets[l], offsets[l + 1]) (offsets int64 [n_lists + 1], non-decreasing, offsets[n_lists] <= n_bpos).
+ * tiles int64 [n_tiles, 3] = (q_lo, q_hi, l): query positions [q_lo, q_hi), 1 to 64 of them, are searched
+ * against the lists probe[l * n_probe + 0 .. n_probe - 1] (probe int32 [n_lists, n_probe], ids < n_lists).
+ * flags: 1 = skip a candidate whose B row equals the query's Q row (Q and B the same matrix), 2 = write the
+ * result of query position p at row q_map[p] (its row of Q, outputs [n_q, k]) instead of at row p
+ * (outputs [n_qpos, k]).  idx_out int32 [., k]: B rows (the original index), -1 where fewer than k
+ * candidates exist; d2_out [., k] squared distances; each row ordered by (d2, index), so the result does
+ * not depend on the probe order and is the same on every run.  1 <= k <= 64; n_q, n_b < 2^31.  Offsets,
+ * probe ids, tiles and row maps are checked on the host first: MDE_E_INVALID before any launch.  SYNC
+ * (the check; the search itself is enqueued). */
+int mde_ann_search(int32_t nf, int32_t k, int32_t flags, int64_t n_q, const float* Q, const float* q_sqn,
+                   int64_t n_qpos, const int32_t* q_map, int64_t n_b, const float* B, const float* b_sqn,
+                   int64_t n_bpos, const int32_t* b_map, int64_t n_lists, const int64_t* offsets,
+                   int32_t n_probe, const int32_t* probe, int64_t n_tiles, const int64_t* tiles,
+                   int32_t* idx_out, float* d2_out, void* stream);
+/* centroids[l] = mean of the rows members[offsets[l] .. offsets[l + 1] - 1] of data [n, nf], summed in
+ * membership order in double (one workgroup per list, no atomics: bit-reproducible); an empty list keeps
+ * the centroid it had.  members int32 [n_members] (< n), offsets as for mde_ann_search (<= n_members),
+ * centroids [n_lists, nf].  Checked on the host first (MDE_E_INVALID before any launch).  SYNC (the check). */
+int mde_ann_centroids(int64_t n, int32_t nf, const float* data, int64_t n_members, const int32_t* members,
+                      int64_t n_lists, const int64_t* offsets, float* centroids, void* stream);
 /* Sparse data matrices (SURVEY 8f rows f2 / f4 on scipy.sparse inputs) [ref: preprocess/data_matrix.py:11-178].
  * Every entry below takes one device CSR of n rows and nf columns: indptr int64 [n + 1], indices int32
  * [nnz] (column ids, strictly increasing within a row), values float32 [nnz]; n < 2^31, nf < 2^31, nnz may

@@ -75,6 +75,10 @@ SYMBOLS = {
     "mde_edges_deduplicate": (c_i32, [c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_edges_count_unique": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_knn": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mde_row_sqnorm": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "mde_ann_search": (c_i32, [c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
+                               c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mde_ann_centroids": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "mde_knn_pairs": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
     "mde_sparse_validate": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_sparse_knn": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),

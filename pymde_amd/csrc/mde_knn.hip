@@ -147,6 +147,16 @@ extern "C" int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int3
   return MDE_OK;
 }
 
+// out[r] = |X[r]|^2 (f32, summed as k_knn's norms are): the row norms the approximate search takes.
+extern "C" int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* out, void* stream) {
+  if (n <= 0 || nf <= 0 || !data || !out) return MDE_E_INVALID;
+  if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
+  hipLaunchKernelGGL(k_row_sqnorm, dim3(mde_grid(n * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, mde_stream(stream),
+                     n, nf, data, out);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
+}
+
 // Directed neighbour lists -> edge list for mde_edges_count_unique: pairs_out[r * k + c] = (r, idx[r][c]).
 // Empty slots (idx < 0) and, when `val` is given, entries with val > max_value become the self pair
 // (r, r), which the edge counter drops [ref: data_matrix.py:147-175 -- neighbours beyond max_distance

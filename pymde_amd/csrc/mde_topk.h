@@ -25,3 +25,28 @@ __device__ __forceinline__ void mde_topk_merge(const float* __restrict__ sd, int
     }
   }
 }
+
+// The merge of the approximate search (mde_ann.hip): candidate c has original index ids[c] and the list is
+// ordered by (d2, index), so the result does not depend on the order in which candidates are offered.
+// Entries of FLT_MAX are empty (padding, self) and never enter.  (worst_d, worst_i) is the k-th entry.
+__device__ __forceinline__ void mde_topk_merge_id(const float* __restrict__ sd, const int* __restrict__ ids,
+                                                  int ncand, int k, float* __restrict__ bd, int* __restrict__ bi,
+                                                  float& worst_d, int& worst_i) {
+  for (int c = 0; c < ncand; ++c) {
+    const float d2 = sd[c];
+    if (d2 >= 3.402823466e+38f) continue;
+    const int id = ids[c];
+    if (d2 < worst_d || (d2 == worst_d && id < worst_i)) {
+      int pos = k - 1;
+      while (pos > 0 && (bd[pos - 1] > d2 || (bd[pos - 1] == d2 && bi[pos - 1] > id))) {
+        bd[pos] = bd[pos - 1];
+        bi[pos] = bi[pos - 1];
+        --pos;
+      }
+      bd[pos] = d2;
+      bi[pos] = id;
+      worst_d = bd[k - 1];
+      worst_i = bi[k - 1];
+    }
+  }
+}

@@ -10,12 +10,16 @@ Same functions as the reference's ``pymde/preprocess/preprocess.py`` [ref: prepr
     complement, no duplicates, no excluded edge, requested count).
 """
 import ctypes
+import logging
 
 import torch
 
 from pymde_amd import _lib
+from pymde_amd import ann as _ann
 from pymde_amd import sparse as _sparse
 from pymde_amd import util
+
+_LOGGER = logging.getLogger("__pymde_amd__")   # problem.LOGGER
 
 
 def _edges_on_device(edges, device=None):
@@ -98,7 +102,8 @@ def _neighbor_lists_to_graph(n, k, idx, values, max_value, device):
     return edges[:count.value], weights[:count.value]
 
 
-def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances=True):
+def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,
+                        n_lists=None, n_probe=None, seed=0, verbose=False):
     """Exact k-nearest-neighbour graph of the rows of a data matrix (Euclidean distance)
     [ref: preprocess/data_matrix.py:91-178] or of the nodes of a ``Graph`` (shortest-path metric,
     ``pymde_amd.graph.k_nearest_neighbors``) [ref: preprocess/generic.py dispatch].
@@ -107,21 +112,42 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     when i and j are neighbours of each other, 1 when only one is a neighbour of the other.
     Neighbours farther than ``max_distance`` do not count (an edge whose both directions are too
     long disappears).  The reference is exact (sklearn brute force) below 10 000 items and
-    approximate (pynndescent) above; this search is exact at every size.  Self matches are
-    excluded by index, so duplicated rows become ordinary zero-distance neighbours.
+    approximate (pynndescent) above; this search is exact at every size unless ``approximate=True``.
+    Self matches are excluded by index, so duplicated rows become ordinary zero-distance neighbours.
+
+    ``approximate=True`` searches data matrices of at least 10 000 rows by an inverted file on the GPU
+    (``pymde_amd.ann``, ``csrc/mde_ann.hip``): k-means (``seed``) splits the rows into ``n_lists`` lists
+    (default round(sqrt(n))), and each row is compared with the rows of the ``n_probe`` lists whose
+    centroids are nearest to its own list's (default min(32, n_lists); ``n_probe >= n_lists`` probes every
+    list and gives the exact graph).  Smaller inputs take the exact kernel.  Recall depends on the data:
+    it is high on clustered data and can be poor on structureless data (an isotropic Gaussian); with
+    ``verbose=True`` the sizes of the lists and a recall@k estimated from 1 000 sampled rows against the
+    exact search are logged.  Sparse inputs are densified (an error if the dense copy does not fit);
+    ``Graph`` inputs have no approximate search.
 
     ``data`` is a dense ``np.ndarray`` / ``torch.Tensor`` [n, n_features], a sparse data matrix (a
     scipy sparse matrix of any format, or a torch sparse COO / CSR tensor; searched by the sparse
     kernel, or densified into the dense one where that is faster, ``_densify_sparse_knn``), or a
     ``Graph``."""
     if hasattr(data, "edges") and hasattr(data, "n_items") and not isinstance(data, torch.Tensor):
+        if approximate:
+            raise ValueError("approximate=True applies to data matrices; a Graph has no approximate search")
         from pymde_amd import graph as _graph
         return _graph.k_nearest_neighbors(data, k, graph_distances=graph_distances,
                                           max_distance=max_distance)
     if _sparse.is_sparse(data):
         csr = _sparse.to_device_csr(data, device)
         k = _clamp_k(k, csr.n)
-        if _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
+        if approximate:
+            _ann.resolve_params(csr.n, n_lists, n_probe)
+        if approximate and csr.n >= _ann.MIN_ITEMS:
+            if not _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
+                raise ValueError(
+                    f"approximate=True densifies sparse data, and the dense copy of this {csr.n} x "
+                    f"{csr.n_features} matrix does not fit in the device memory allowed for it; "
+                    "use approximate=False (the exact sparse kernel)")
+            idx, d2 = _approximate_knn_lists(csr.to_dense(), k, n_lists, n_probe, seed, verbose)
+        elif _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
             idx, d2 = _dense_knn_lists(csr.to_dense(), k)
         else:
             idx, d2 = _sparse_knn_lists(csr, k)
@@ -135,7 +161,12 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     data = data.to(device=device, dtype=torch.float32).contiguous()
     n = int(data.shape[0])
     k = _clamp_k(k, n)
-    idx, d2 = _dense_knn_lists(data, k)
+    if approximate:
+        _ann.resolve_params(n, n_lists, n_probe)      # the same argument checks at every size
+    if approximate and n >= _ann.MIN_ITEMS:
+        idx, d2 = _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
+    else:
+        idx, d2 = _dense_knn_lists(data, k)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
     return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
 
@@ -161,6 +192,33 @@ def _dense_knn_lists(data, k):
         _lib.check(lib.mde_knn(n, nf, _lib.ptr(data), k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(sqn),
                                _lib.stream_ptr(device)))
     return idx, d2
+
+
+def _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose):
+    """Directed neighbour lists of a dense float32 [n, nf] on the GPU by the inverted-file search."""
+    n_lists, n_probe = _ann.resolve_params(int(data.shape[0]), n_lists, n_probe)
+    if k > _ann.MAX_K:      # the exact kernel's error, before any work
+        raise _lib.MdeHipError(_lib.MDE_E_INVALID, "mde_ann_search: invalid arguments (1 <= k <= %d)" % _ann.MAX_K)
+    stats = {} if verbose else None
+    with torch.cuda.device(data.device):
+        idx, d2 = _ann.knn_lists(data, k, n_lists=n_lists, n_probe=n_probe, seed=seed, timings=stats)
+    if verbose:
+        sizes = stats["list_sizes"].double()
+        _LOGGER.info(
+            f"approximate {k}-NN: {n_lists} lists (sizes min {int(sizes.min())}, median "
+            f"{int(sizes.median())}, max {int(sizes.max())}), {n_probe} probed per list, "
+            f"{stats['candidate_pairs'] / float(data.shape[0]) ** 2:.3f} of all pairs scanned in "
+            f"{stats['tiles']} tiles (estimated load imbalance {stats['imbalance']:.2f})")
+        recall = _estimated_recall(data, idx, k, seed=seed)
+        _LOGGER.info(f"approximate {k}-NN: estimated recall@{k} {recall:.3f} (1000 sampled rows)")
+    return idx, d2
+
+
+def _estimated_recall(data, idx, k, n_samples=1000, seed=0):
+    """Recall@k of neighbour lists idx [n, k] of dense float32 data on the GPU, estimated on ``n_samples``
+    seeded random rows against the exact query-against-base search."""
+    with torch.cuda.device(data.device):
+        return _ann.sampled_recall(data, idx, k, n_samples=n_samples, seed=seed)
 
 
 def _sparse_knn_lists(csr, k):

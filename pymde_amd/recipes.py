@@ -125,15 +125,23 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
 def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p,
                        repulsive_penalty=penalties.Log, constraint=None, n_neighbors=None,
                        repulsive_fraction=None, max_distance=None, init="quadratic", device=None,
-                       verbose=False, seed=None):
+                       verbose=False, seed=None, approximate_neighbors=False):
     """An MDE problem that preserves the k-nearest-neighbour structure of a data matrix
     (rows = items) [ref: recipes.py:221-448]: k-NN graph (weights 1 / 2), optional spectral
     initialisation, uniformly sampled repulsive edges (weight -1), ``PushAndPull`` of the two
     penalties.  ``data`` is a dense ``np.ndarray`` / ``torch.Tensor``, a sparse data matrix (scipy
     sparse or a torch sparse COO / CSR tensor; a data matrix, not an adjacency matrix), or a
     ``Graph``: neighbourhoods are then taken under its shortest-path metric.  Every stage runs on the
-    GPU (rows f2, f3, a10, f1 of SURVEY section 8)."""
+    GPU (rows f2, f3, a10, f1 of SURVEY section 8).
+
+    ``approximate_neighbors`` (data matrices only): ``True`` builds the k-NN graph by the approximate
+    inverted-file search of ``preprocess.k_nearest_neighbors(approximate=True)`` with its defaults, a dict
+    ``{"n_lists": .., "n_probe": ..}`` sets those knobs; ``False`` (the default) keeps the exact search.
+    Recall depends on the data; ``verbose=True`` logs an estimate."""
     is_graph = isinstance(data, _graph.Graph)
+    knn_options = _approximate_options(approximate_neighbors)
+    if is_graph and knn_options:
+        raise ValueError("approximate_neighbors applies to data matrices; a Graph has no approximate search")
     if not is_graph and not isinstance(data, torch.Tensor) and not _sparse.is_sparse(data):
         data = torch.as_tensor(data)
     if device is None:
@@ -165,8 +173,11 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
         edges, weights = _graph.k_nearest_neighbors(data, k=n_neighbors, graph_distances=True,
                                                           max_distance=max_distance, verbose=verbose)
     else:
+        if knn_options:
+            knn_options.setdefault("seed", 0 if seed is None else seed)
+            knn_options["verbose"] = verbose
         edges, weights = preprocess.k_nearest_neighbors(data, k=n_neighbors, max_distance=max_distance,
-                                                        device=device)
+                                                        device=device, **knn_options)
     if isinstance(constraint, constraints.Anchored):
         edges, weights = _remove_anchor_anchor_edges(edges, weights, constraint.anchors)
     if init == "quadratic":
@@ -207,11 +218,29 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     return mde
 
 
+def _approximate_options(approximate_neighbors):
+    """Keywords of ``preprocess.k_nearest_neighbors`` for a recipe's ``approximate_neighbors`` value:
+    False -> {} (the exact search), True -> approximate with the defaults, a dict -> approximate with
+    its ``n_lists`` / ``n_probe``."""
+    if approximate_neighbors is None or approximate_neighbors is False:
+        return {}
+    if approximate_neighbors is True:
+        return {"approximate": True}
+    if isinstance(approximate_neighbors, dict):
+        unknown = set(approximate_neighbors) - {"n_lists", "n_probe"}
+        if unknown:
+            raise ValueError(f"approximate_neighbors: unknown keys {sorted(unknown)}; "
+                             "the knobs are 'n_lists' and 'n_probe'")
+        return dict(approximate_neighbors, approximate=True)
+    raise ValueError("approximate_neighbors must be True, False or a dict {'n_lists': .., 'n_probe': ..}")
+
+
 def laplacian_embedding(data, embedding_dim=2, n_neighbors=None, max_distance=None, init="quadratic",
-                        device=None, verbose=False):
+                        device=None, verbose=False, approximate_neighbors=False):
     """An MDE problem whose solution is a Laplacian embedding [ref: recipes.py:451-503]: the k-NN
     graph of ``preserve_neighbors`` with quadratic penalties, no repulsion and the standardization
-    constraint.  ``data`` as for ``preserve_neighbors`` (dense, sparse or a ``Graph``)."""
+    constraint.  ``data`` and ``approximate_neighbors`` as for ``preserve_neighbors``."""
     return preserve_neighbors(data, embedding_dim=embedding_dim, attractive_penalty=penalties.Quadratic,
                               repulsive_penalty=None, n_neighbors=n_neighbors, max_distance=max_distance,
-                              init=init, device=device, verbose=verbose)
+                              init=init, device=device, verbose=verbose,
+                              approximate_neighbors=approximate_neighbors)
