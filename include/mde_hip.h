@@ -223,6 +223,11 @@ int mde_plan_expand_layout(const mde_plan* plan, int32_t layout, const float* in
  * [10] row blocks PERMUTED (rows dealt to the blocks by degree; every entry adds f / 2), [11] hub rows PEELED off to
  * the CSR hub kernel, [12] their half-edges, [13] their segments, [14], [15] reserved (0). */
 int mde_plan_ring_info(const mde_plan* plan, int64_t* info_host);
+/* Checks the lane-stable pairs of the LDS-ring layout on the device: out_host[0] = entries of a pair's second wave
+ * iteration whose row the first iteration holds on another lane (0 in every layout the builder emits: the kernel reads
+ * both accumulators of a pair before it writes either), [1] = rows held by both iterations of a pair, [2] = pairs.
+ * All zero when no layout is built.  SYNC. */
+int mde_plan_ring_check(const mde_plan* plan, int64_t* out_host, void* stream);
 /* Processing order of the plan's rows for the general-d kernel (d = 5 .. 512; round 6).  The reference evaluates
  * the edges in the caller's order whatever the numbering of the items [ref: pymde/average_distortion.py:62-106]; here
  * the rows of X gathered at the same time share the caches only when neighbours are close in the order the rows are

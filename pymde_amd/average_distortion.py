@@ -130,6 +130,16 @@ class EdgePlan(object):
         out["built"], out["permuted"] = bool(out["built"]), bool(out["permuted"])
         return out
 
+    def ring_check(self):
+        """Device check of the LDS-ring layout's lane-stable pairs (``mde_plan_ring_check``): ``split`` entries whose
+        row the other iteration of their pair holds on another lane (always 0), ``shared`` rows held by both
+        iterations of a pair, ``pairs`` checked."""
+        lib = _lib.load()
+        out = (ctypes.c_int64 * 3)()
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mde_plan_ring_check(self._handle, out, _lib.stream_ptr(self.device)))
+        return {"split": int(out[0]), "shared": int(out[1]), "pairs": int(out[2])}
+
     def row_order(self, mode=1):
         """Build (mode 1: keep if it helps, 2: keep regardless) or drop (0) the breadth-first processing order of the
         rows that the general-d kernel walks (``mde_plan_row_order``); returns a dict with ``in_use``, the mean distance

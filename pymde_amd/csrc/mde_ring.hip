@@ -542,6 +542,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
                                                          uint32_t* __restrict__ packed,
                                                          int32_t* __restrict__ peid, uint32_t* __restrict__ hdr) {
   __shared__ uint8_t s_taken[MDE_BLOCK / 64][64], s_free[MDE_BLOCK / 64][64];
+  __shared__ uint32_t s_prow[MDE_BLOCK / 64][64];  // the rows of a pair's first iteration, by lane
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t nw = ((int64_t)gridDim.x * MDE_BLOCK) >> 6;
   const uint32_t JM = (1u << JB) - 1u;
@@ -580,18 +581,51 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
       rcls = (int)((rowaddr >> sh) & (uint32_t)cm);
     }
     s_taken[wv][lane] = 0;
+    s_prow[wv][lane] = 0xffffffffu;
     __syncthreads();
+    // Lane-stable pairs: the kernel reads both accumulators of a pair of iterations before it writes either, so
+    // a row that occurs in both iterations must sit on the SAME lane in both (the second takes the first's
+    // updated value from a register there).  The first iteration of a pair (even `it`, wave wv) is dealt as
+    // before; the second (wave wv + 1 of the same trip: itb is a multiple of 4) pins such entries to the first's
+    // lanes and deals the others as they fall -- an entry whose lane a pinned one took moves to a free lane.
+    const bool second = (it & 1) != 0;
     int l = lane;
-    if (place) l = ring_place_wave(act, rcls, lane);
-    if (act) s_taken[wv][l] = 1;
+    if (!second) {
+      if (place) l = ring_place_wave(act, rcls, lane);
+      if (act) {
+        s_taken[wv][l] = 1;
+        s_prow[wv][l] = rowaddr;
+      }
+    }
+    __syncthreads();
+    int pin = -1;
+    if (second) {
+      const uint32_t prow = s_prow[wv - 1][lane];
+#pragma unroll 8
+      for (int k = 0; k < 64; ++k)
+        if ((uint32_t)__builtin_amdgcn_readlane((int)prow, k) == rowaddr) pin = k;
+      pin = act ? pin : -1;
+      if (place) l = ring_place_wave(act && pin < 0, rcls, lane);
+      if (pin >= 0) {
+        l = pin;
+        s_taken[wv][l] = 1;
+      }
+    }
+    __syncthreads();
+    // (the unpinned entries' lanes are distinct: each one tests and takes its own)
+    const bool moved = second && act && pin < 0 && s_taken[wv][l];
+    if (second && act && !moved) s_taken[wv][l] = 1;
     __syncthreads();
     {
-      // the lanes nobody took, in ascending order, for the padding entries
+      // the lanes nobody took, in ascending order: first for the moved entries, then for the padding entries
       const bool fr = !s_taken[wv][lane];
       const unsigned long long fm = __ballot(fr);
       if (fr) s_free[wv][__popcll(fm & ((1ull << lane) - 1ull))] = (uint8_t)lane;
     }
     __syncthreads();
+    const unsigned long long mvm = __ballot(moved);
+    const int nmoved = __popcll(mvm);
+    if (moved) l = s_free[wv][__popcll(mvm & ((1ull << lane) - 1ull))];
     // whose loss terms: the entry whose row is the smaller vertex of the edge (grow is the local row there); a
     // permuted layout (grow is a slot) adds every entry's with weight 1/2
     const bool counts = act && (count_all || (uint32_t)(row_lo + grow) < col);
@@ -611,7 +645,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
       peid[base + (size_t)l * 4] = eid[q];
     } else if (valid) {
       // padding: a dummy row slot of the lane's own bank class, a resident column
-      const int lf = s_free[wv][lane - cnt];
+      const int lf = s_free[wv][nmoved + lane - cnt];
       packed[base + (size_t)lf * 4] = ring_pack_word(d, (uint32_t)(R + (lf & 31)) * 4u * (uint32_t)d,
                                                      (uint32_t)ring_off + (mpad % (uint32_t)S) * cbytes);
       peid[base + (size_t)lf * 4] = -1;
@@ -1876,6 +1910,60 @@ extern "C" int mde_plan_ring_info(const mde_plan* plan, int64_t* info) {
   info[11] = L.n_hub_rows;
   info[12] = L.hub_half_edges;
   info[13] = L.n_hub_segs;
+  return MDE_OK;
+}
+
+// One wave per pair of iterations (it, it + 1), it even: a real row (address below the dummy rows) of the second
+// iteration that the first holds on ANOTHER lane breaks the kernel's accumulator read-ahead.  out[0] += such
+// entries, out[1] += real rows held by both iterations (on one lane), out[2] += pairs checked.
+__global__ __launch_bounds__(MDE_BLOCK) void k_ring_pair_check(int64_t npairs, const uint32_t* __restrict__ packed, int d, int R,
+                                                               unsigned long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = ((int64_t)gridDim.x * MDE_BLOCK) >> 6;
+  const uint32_t mask = d == 2 ? 0xfff8u : 0xfffcu, dummy = (uint32_t)R * 4u * (uint32_t)d;
+  unsigned long long split = 0, shared = 0, pairs = 0;
+  for (int64_t pr = ((int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x) >> 6; pr < npairs; pr += nw) {
+    const int64_t it = 2 * pr;
+    const size_t base = ((size_t)(it >> 2) * 64 + (size_t)lane) * 4 + (size_t)(it & 3);
+    const uint32_t ra = packed[base] & mask, rb = packed[base + 1] & mask;
+    int found = -1;
+    for (int k = 0; k < 64; ++k)
+      if ((uint32_t)__builtin_amdgcn_readlane((int)ra, k) == rb) found = k;
+    const bool real = rb < dummy;
+    split += __popcll(__ballot(real && found >= 0 && found != lane));
+    shared += __popcll(__ballot(real && found >= 0));
+    ++pairs;
+  }
+  if (lane == 0) {
+    atomicAdd(&out[0], split);
+    atomicAdd(&out[1], shared);
+    atomicAdd(&out[2], pairs);
+  }
+}
+
+extern "C" int mde_plan_ring_check(const mde_plan* plan, int64_t* out_host, void* stream) {
+  if (!plan || !out_host) return MDE_E_INVALID;
+  const mde_ring_layout& L = plan->ring;
+  for (int i = 0; i < 3; ++i) out_host[i] = 0;
+  if (!L.packed || L.n_iters == 0) return MDE_OK;
+  hipStream_t st = mde_stream(stream);
+  unsigned long long* dout = nullptr;
+  hipError_t e = hipMalloc(&dout, 3 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemsetAsync(dout, 0, 3 * sizeof(unsigned long long), st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_ring_pair_check, dim3(mde_grid(L.n_iters / 2 * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st,
+                       L.n_iters / 2, L.packed, L.d, L.rows_per_block, dout);
+    e = hipGetLastError();
+  }
+  unsigned long long h[3] = {0, 0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(h, dout, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (dout) (void)hipFree(dout);
+  if (e != hipSuccess) {
+    mde_set_error("mde_plan_ring_check: %s", hipGetErrorString(e));
+    return MDE_E_HIP;
+  }
+  for (int i = 0; i < 3; ++i) out_host[i] = (int64_t)h[i];
   return MDE_OK;
 }
 

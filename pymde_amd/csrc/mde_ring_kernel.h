@@ -693,9 +693,11 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
       // Software pipeline over PAIRS of iterations.  In the region of pair p the wave (after the
       // hand-shake for the chunks of pair p + 1) issues the LDS reads of the operands of pair p + 1
       // (x_v, x_u, parameter), then evaluates the two iterations of pair p (operands read one pair
-      // ago): accumulator write of k and, right behind it, the accumulator read of k + 1 (the LDS
-      // executes a wave's accesses in order, so a row shared by consecutive iterations sees the
-      // update).  Every LDS access of the loop is a compiler-counted instruction (the control-word
+      // ago) with both accumulators read at the end of the previous region -- the LDS executes a wave's
+      // accesses in order, so they see the previous pair's writes, and the layout keeps a row shared by
+      // the two iterations of a pair on one lane, which forwards it in a register: no LDS round trip is
+      // exposed inside a region and the operand reads of pair p + 1 stay in flight (counted waits).
+      // Every LDS access of the loop is a compiler-counted instruction (the control-word
       // store included: round 3 issued it from inline asm, which put hipcc's lgkmcnt counts off by
       // one), and the region of a pair is ONE basic block: hipcc's scheduler interleaves the two
       // evaluations and places the waits.
@@ -705,7 +707,7 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
       // hand-shake branch per pair, one loss-class branch per block of four (three copies of the
       // block body), and no header word through an SGPR.
       Pre xa, xb;  // operands of the pair being evaluated
-      float acc[D];
+      float acc[D], accb[D];  // accumulators of its two rows, both read at the end of the previous region
       auto block_body = [&](auto lc_tag, int u, int b) __attribute__((always_inline)) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -724,9 +726,17 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
           const uint32_t hma = lc2 ? (uint32_t)__builtin_amdgcn_readlane((int)hv[u], 4 * q) : 0u;
           const uint32_t hmb = lc2 ? (uint32_t)__builtin_amdgcn_readlane((int)hv[u], 4 * q + 4) : 0u;
           finish(lc_tag, pq[u][q], xa, acc, p1a, hma);
-          if (HAS_GRAD) ring_ld<D>(L + GR_OFF + row_of(pq[u][q + 1]), acc);
-          finish(lc_tag, pq[u][q + 1], xb, acc, p1b, hmb);
-          if (HAS_GRAD) ring_ld<D>(L + GR_OFF + row_of(pq[un][qn]), acc);
+          if (HAS_GRAD) {
+            // (lane-stable pairs, k_ring_pack: a row of both iterations sits on this lane in both -- the value is here)
+            const bool same = row_of(pq[u][q + 1]) == row_of(pq[u][q]);
+#pragma unroll
+            for (int c = 0; c < D; ++c) accb[c] = same ? acc[c] : accb[c];
+          }
+          finish(lc_tag, pq[u][q + 1], xb, accb, p1b, hmb);
+          if (HAS_GRAD) {
+            ring_ld<D>(L + GR_OFF + row_of(pq[un][qn]), acc);
+            ring_ld<D>(L + GR_OFF + row_of(pq[un][qn + 1]), accb);
+          }
           xa = xna;
           xb = xnb;
         }
@@ -739,7 +749,10 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
       xb = issue_x(pq[0][1], (a0_scalar || PS != 0) ? a0s : wq[0][1], bx4(bq[0], 1));
       release_to(0, 2);
       prefetch_landed();
-      if (HAS_GRAD) ring_ld<D>(L + GR_OFF + row_of(pq[0][0]), acc);
+      if (HAS_GRAD) {
+        ring_ld<D>(L + GR_OFF + row_of(pq[0][0]), acc);
+        ring_ld<D>(L + GR_OFF + row_of(pq[0][1]), accb);
+      }
       for (int base = 0; base < NB; base += PFB) {
 #pragma unroll
         for (int u = 0; u < PFB; ++u) {
@@ -802,14 +815,27 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
           __hip_atomic_store(&sync[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
-        for (int sl = tid; sl < R; sl += BS) {
-          const int r = sr[sl];
-          if (r < 0) continue;
+        // eight slots per thread and trip: their rows' loads all in flight before the first is used (a slot
+        // without a row loads row 0 and drops it)
+        for (int s0 = 0; s0 < R; s0 += 8 * BS) {
+          int rr[8];
+          float o[8][D];
 #pragma unroll
-          for (int c = 0; c < D; ++c) {
-            const float o = __hip_atomic_load(other + (size_t)r * D + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float m = GR[sl * D + c];
-            grad[(size_t)(row_lo + r) * D + c] = (qg == 0 ? m + o : o + m) * grad_scale;  // (group order)
+          for (int k = 0; k < 8; ++k) rr[k] = s0 + tid + k * BS < R ? sr[s0 + tid + k * BS] : -1;
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int c = 0; c < D; ++c)
+              o[k][c] = __hip_atomic_load(other + (size_t)max(rr[k], 0) * D + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            if (rr[k] < 0) continue;
+            const int sl = s0 + tid + k * BS;
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+              const float m = GR[sl * D + c];
+              grad[(size_t)(row_lo + rr[k]) * D + c] = (qg == 0 ? m + o[k][c] : o[k][c] + m) * grad_scale;  // (group order)
+            }
           }
         }
       }
@@ -841,14 +867,21 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
     float* mine = partial + ((size_t)qg * nloc + r0) * D;
     const float* other = partial + ((size_t)(1 - qg) * nloc + r0) * D;
     float* grow = grad + (size_t)(row_lo + r0) * D;
+    // The rows as 16-byte pieces where every side is aligned to them, the rest element by element: the partial
+    // rows go out as write-through stores and come back in batches of eight device-scope loads per thread and
+    // trip, under one wait (a loop of relaxed atomic loads waited for each before the next: 11 dependent round
+    // trips per thread at config 4), the gradient rows as 16-byte stores.
+    static_assert(GR_OFF % 16 == 0, "16-byte accumulator pieces");
+    const bool vec = ((reinterpret_cast<uintptr_t>(mine) | reinterpret_cast<uintptr_t>(other) | reinterpret_cast<uintptr_t>(grow)) & 15) == 0;
+    const int n4 = vec ? (nr * D) >> 2 : 0, n1 = nr * D;
+    const ring_f4* GR4 = reinterpret_cast<const ring_f4*>(GR);
     if (!second) {
-      if constexpr (D == 2) {
-        for (int i = tid; i < nr; i += BS)
-          __hip_atomic_store(reinterpret_cast<double*>(mine) + i, reinterpret_cast<const double*>(GR)[i], __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        for (int i = tid; i < nr * D; i += BS) __hip_atomic_store(mine + i, GR[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int i = tid; i < n4; i += BS) {
+        // (agent scope, write-through: what __hip_atomic_store relaxed / agent emits, 16 bytes wide)
+        const ring_f4 v4 = GR4[i];
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(reinterpret_cast<ring_f4*>(mine) + i), "v"(v4) : "memory");
       }
+      for (int i = (n4 << 2) + tid; i < n1; i += BS) __hip_atomic_store(mine + i, GR[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows have completed
       __syncthreads();
       if (tid == 0) __hip_atomic_store(&sync[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -860,21 +893,31 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
         __hip_atomic_store(&sync[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       __syncthreads();
-      if constexpr (D == 2) {
-        for (int i = tid; i < nr; i += BS) {
-          const double o = __hip_atomic_load(reinterpret_cast<const double*>(other) + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const float2 ov = *reinterpret_cast<const float2*>(&o);
-          const float2 mv = reinterpret_cast<const float2*>(GR)[i];
-          // (group order, as k_ring_combine adds them)
-          float2 r;
-          r.x = (qg == 0 ? mv.x + ov.x : ov.x + mv.x) * grad_scale;
-          r.y = (qg == 0 ? mv.y + ov.y : ov.y + mv.y) * grad_scale;
-          reinterpret_cast<float2*>(grow)[i] = r;
+      // (group order, as k_ring_combine adds them; the loads are clamped, so every one is in bounds)
+      const ring_f4* o4p = reinterpret_cast<const ring_f4*>(other);
+      for (int i0 = 0; i0 < n4; i0 += 8 * BS) {
+        ring_f4 o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(o[k]) : "v"(o4p + min(i0 + tid + k * BS, n4 - 1)) : "memory");
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]), "+v"(o[6]), "+v"(o[7])::"memory");
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int i = i0 + tid + k * BS;
+          if (i < n4) {
+            const ring_f4 m = GR4[i];
+            reinterpret_cast<ring_f4*>(grow)[i] = (qg == 0 ? m + o[k] : o[k] + m) * grad_scale;
+          }
         }
-      } else {
-        for (int i = tid; i < nr * D; i += BS) {
-          const float o = __hip_atomic_load(other + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          grow[i] = (qg == 0 ? GR[i] + o : o + GR[i]) * grad_scale;
+      }
+      for (int i0 = n4 << 2; i0 < n1; i0 += 8 * BS) {
+        float o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = __hip_atomic_load(other + min(i0 + tid + k * BS, n1 - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int i = i0 + tid + k * BS;
+          if (i < n1) grow[i] = (qg == 0 ? GR[i] + o[k] : o[k] + GR[i]) * grad_scale;
         }
       }
     }
@@ -883,7 +926,10 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
     // Q == 1: the rows are final.  Q > 1: unscaled per-group partials, summed by k_ring_combine
     float* grow = (Q == 1) ? grad + (size_t)(row_lo + r0) * D : partial + ((size_t)qg * nloc + r0) * D;
     const float sc = (Q == 1) ? grad_scale : 1.0f;
-    for (int i = tid; i < nr * D; i += BS) grow[i] = GR[i] * sc;
+    // (16-byte stores where the rows are aligned to them)
+    const int n4 = (reinterpret_cast<uintptr_t>(grow) & 15) == 0 ? (nr * D) >> 2 : 0;
+    for (int i = tid; i < n4; i += BS) reinterpret_cast<ring_f4*>(grow)[i] = reinterpret_cast<const ring_f4*>(GR)[i] * sc;
+    for (int i = (n4 << 2) + tid; i < nr * D; i += BS) grow[i] = GR[i] * sc;
   }
   // block-wide loss partial (the x_v region is free now), then the loss itself: the last
   // workgroup to arrive adds the partials of all of them in a fixed order (no second launch).  The
