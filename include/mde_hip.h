@@ -264,6 +264,30 @@ int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_ou
             float* sqn_work, void* stream);
 /* out[r] = |data[r]|^2 for the rows of data [n, nf] (f32; the norms mde_knn forms internally). */
 int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* out, void* stream);
+/* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
+ * scipy.spatial.distance.  The reference has no metric keyword. */
+#define MDE_METRIC_EUCLIDEAN 0
+#define MDE_METRIC_COSINE 1      /* 1 - u.v / (|u| |v|)                  */
+#define MDE_METRIC_CORRELATION 2 /* cosine of the row-centred vectors    */
+#define MDE_METRIC_MANHATTAN 3   /* sum |u - v|                          */
+/* Exact k nearest neighbours under the Manhattan distance, same contract as mde_knn except that d_out
+ * [n, k] holds the distances themselves (not squares): idx_out [n, k] int32 (self excluded by index; -1
+ * when fewer than k other rows exist), ascending per row, ties to the smaller index; 1 <= k <= 64. */
+int mde_knn_l1(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_out, float* d_out,
+               void* stream);
+/* out [n, nf] = the rows of data scaled to unit length, centred first when center != 0: the Euclidean
+ * search on `out` ranks by cosine (correlation) distance, d2 = 2 (1 - cos).  deg_out: int32 [2] on the
+ * device = (number of rows without a direction -- zero norm, or constant when centring --, index of the
+ * first such row; INT32_MAX when there is none); those rows come out all zero, never NaN.  out may be
+ * NULL (the check alone). */
+int mde_rows_normalize(int64_t n, int32_t nf, const float* data, int32_t center, float* out,
+                       int32_t* deg_out, void* stream);
+/* out[e] = distance under `metric` (MDE_METRIC_COSINE, _CORRELATION or _MANHATTAN) between rows i and j of data [n, nf] for every edge
+ * (i, j) of edges [p, 2] (int64): one pass over the two rows, sums in double, no normalised copy, so
+ * near-duplicate rows keep their small distances.  NaN for an endpoint outside [0, n) and where the
+ * distance is undefined (a zero row under cosine, a constant row under correlation). */
+int mde_pair_distances_metric(int64_t n, int32_t nf, const float* data, int64_t p, const int64_t* edges,
+                              int32_t metric, float* out, void* stream);
 /* Approximate k-NN by an inverted file (csrc/mde_ann.hip) [ref: preprocess/data_matrix.py:125-143].
  * Query-against-base search restricted to block-sparse (query tile, candidate range) pairs.  Query
  * position p reads row q_map[p] of Q [n_q, nf] (q_map NULL: row p), base position c reads row b_map[c] of
@@ -309,6 +333,12 @@ int mde_sparse_knn(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, co
  * endpoint outside [0, n) gives NaN.  Reproducible from run to run.  SYNC (the validation). */
 int mde_sparse_distances(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
                          const float* values, int64_t p, const int64_t* edges, float* out, void* stream);
+/* values_out[e] = values[e] / |row of e|: the CSR with unit rows (same indptr / indices), on which
+ * mde_sparse_knn / mde_sparse_distances rank by cosine, d2 = 2 (1 - cos).  deg_out: int32 [2] on the device
+ * = (number of rows with zero norm, index of the first; INT32_MAX when none).  SYNC (the validation). */
+int mde_sparse_rows_normalize(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr,
+                              const int32_t* indices, const float* values, float* values_out,
+                              int32_t* deg_out, void* stream);
 /* Shortest-path distances on the graph whose edges built `plan` (a FULL plan; its symmetrised CSR
  * is the adjacency) [ref: preprocess/graph.py:286-474, _graph.pyx:10-52].
  * w: per-half-edge edge lengths in plan (CSR) order (mde_plan_expand), or NULL for unit lengths

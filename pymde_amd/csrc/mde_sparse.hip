@@ -385,3 +385,51 @@ extern "C" int mde_sparse_distances(int64_t n, int32_t nf, int64_t nnz, const in
   MDE_LAUNCH_CHECK();
   return MDE_OK;
 }
+
+// ------------------------------------------------------------------ unit rows (cosine)
+// values_out[e] = values[e] / |row of e| (one wave per row, the norm summed in double): the Euclidean
+// kernels above then rank by cosine, d2 = 2 (1 - cos), and the sparsity pattern is kept.  A row without a
+// positive norm (empty: explicit zeros are not stored) is counted in deg[0], its index min-reduced into
+// deg[1], and its values become zero, never NaN.
+__global__ __launch_bounds__(MDE_BLOCK) void k_sparse_rows_normalize(int64_t n, const int64_t* __restrict__ indptr,
+                                                                     const float* __restrict__ values,
+                                                                     float* __restrict__ out, int* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = ((int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * MDE_BLOCK) >> 6;
+  for (int64_t r = w0; r < n; r += nw) {
+    const int64_t lo = indptr[r], hi = indptr[r + 1];
+    double q = 0.0;
+    for (int64_t e = lo + lane; e < hi; e += 64) {
+      const double v = values[e];
+      q += v * v;
+    }
+    q = mde_wave_sum(q);
+    const bool bad = !(q > 0.0) || !(q < 1.0e300);
+    const float inv = bad ? 0.0f : (float)(1.0 / sqrt(q));
+    for (int64_t e = lo + lane; e < hi; e += 64) out[e] = values[e] * inv;
+    if (bad && lane == 0) {
+      atomicAdd(deg, 1);
+      atomicMin(deg + 1, (int)r);
+    }
+  }
+}
+
+extern "C" int mde_sparse_rows_normalize(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr,
+                                         const int32_t* indices, const float* values, float* values_out,
+                                         int32_t* deg_out, void* stream) {
+  if (!deg_out || (nnz > 0 && !values_out)) {
+    mde_set_error("mde_sparse_rows_normalize: invalid arguments (non-null values_out / deg_out)");
+    return MDE_E_INVALID;
+  }
+  hipStream_t st = mde_stream(stream);
+  const int rc = spk_validate("mde_sparse_rows_normalize", n, nf, nnz, indptr, indices, values, st);
+  if (rc != MDE_OK) return rc;
+  const int32_t init[2] = {0, 0x7fffffff};
+  MDE_HIP(hipMemcpyAsync(deg_out, init, sizeof(init), hipMemcpyHostToDevice, st));
+  MDE_HIP(hipStreamSynchronize(st));        // `init` lives on this stack
+  hipLaunchKernelGGL(k_sparse_rows_normalize, dim3(mde_grid(n * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n,
+                     indptr, values, values_out, deg_out);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
+}

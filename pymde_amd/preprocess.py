@@ -16,6 +16,7 @@ import torch
 
 from pymde_amd import _lib
 from pymde_amd import ann as _ann
+from pymde_amd import metrics as _metrics
 from pymde_amd import sparse as _sparse
 from pymde_amd import util
 
@@ -103,8 +104,8 @@ def _neighbor_lists_to_graph(n, k, idx, values, max_value, device):
 
 
 def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,
-                        n_lists=None, n_probe=None, seed=0, verbose=False):
-    """Exact k-nearest-neighbour graph of the rows of a data matrix (Euclidean distance)
+                        n_lists=None, n_probe=None, seed=0, verbose=False, metric="euclidean"):
+    """Exact k-nearest-neighbour graph of the rows of a data matrix (Euclidean distance by default)
     [ref: preprocess/data_matrix.py:91-178] or of the nodes of a ``Graph`` (shortest-path metric,
     ``pymde_amd.graph.k_nearest_neighbors``) [ref: preprocess/generic.py dispatch].
 
@@ -128,13 +129,30 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     ``data`` is a dense ``np.ndarray`` / ``torch.Tensor`` [n, n_features], a sparse data matrix (a
     scipy sparse matrix of any format, or a torch sparse COO / CSR tensor; searched by the sparse
     kernel, or densified into the dense one where that is faster, ``_densify_sparse_knn``), or a
-    ``Graph``."""
+    ``Graph``.
+
+    ``metric`` (data matrices only): ``"euclidean"`` (``"l2"``), ``"cosine"``, ``"correlation"`` or
+    ``"manhattan"`` (``"l1"``, ``"cityblock"``), defined as in ``scipy.spatial.distance``; ``max_distance``
+    is in the metric's own units and the weights keep their meaning.  Cosine and correlation search a
+    normalised (centred and normalised) float32 copy of the data -- ``4 n n_features`` bytes beside the
+    data -- with the Euclidean kernels, exact or approximate; a sparse matrix keeps its sparsity under
+    cosine (its rows are scaled in place of a copy) and is densified under correlation and Manhattan (an
+    error if the dense copy does not fit).  Manhattan has an exact kernel of its own and no approximate
+    search.  A row without a direction (all zero under cosine, constant under correlation) is an error.
+    See ``pymde_amd.metrics``."""
+    metric = _metrics.resolve(metric)
+    _metrics.check_approximate(metric, approximate)
     if hasattr(data, "edges") and hasattr(data, "n_items") and not isinstance(data, torch.Tensor):
+        _metrics.check_graph(metric)
         if approximate:
             raise ValueError("approximate=True applies to data matrices; a Graph has no approximate search")
         from pymde_amd import graph as _graph
         return _graph.k_nearest_neighbors(data, k, graph_distances=graph_distances,
                                           max_distance=max_distance)
+    if metric != _metrics.EUCLIDEAN:
+        idx, values, bound = _metric_knn_lists(data, k, metric, max_distance, device, approximate, n_lists,
+                                               n_probe, seed, verbose)
+        return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
     if _sparse.is_sparse(data):
         csr = _sparse.to_device_csr(data, device)
         k = _clamp_k(k, csr.n)
@@ -169,6 +187,57 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
         idx, d2 = _dense_knn_lists(data, k)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
     return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
+
+
+def _metric_knn_lists(data, k, metric, max_distance=None, device=None, approximate=False, n_lists=None,
+                      n_probe=None, seed=0, verbose=False):
+    """Directed neighbour lists of a data matrix under cosine, correlation or Manhattan (a canonical name):
+    ``(idx [n, k] int32, values [n, k], bound)``.  ``values`` are what the kernels rank by -- the squared
+    chord ``d2 = 2 (1 - cos)`` of the unit rows for cosine / correlation, the distance itself for Manhattan
+    -- and ``bound`` is ``max_distance`` in those units (None without one): the lists become a graph
+    without a pass that converts them."""
+    sparse_kernel = metric == _metrics.COSINE    # the others need the dense copy
+    csr = None
+    if _sparse.is_sparse(data):
+        csr = _sparse.to_device_csr(data, device)
+        n, device = csr.n, csr.device
+        if metric == _metrics.COSINE:
+            csr = _metrics.normalized_csr(csr)
+        needs_dense = not sparse_kernel or (approximate and n >= _ann.MIN_ITEMS)
+        if _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, device):
+            data, csr = csr.to_dense(), None
+        elif needs_dense:
+            raise ValueError(
+                f"metric='{metric}'" + (" with approximate=True" if sparse_kernel else "") + " densifies sparse "
+                f"data, and the dense copy of this {csr.n} x {csr.n_features} matrix does not fit in the device "
+                "memory allowed for it; " + ("use approximate=False (the exact sparse kernel)" if sparse_kernel
+                                             else "metric='cosine' and 'euclidean' have a sparse kernel"))
+    else:
+        if not isinstance(data, torch.Tensor):
+            data = torch.as_tensor(data)
+        if device is None:
+            device = data.device if data.is_cuda else util.get_default_device()
+        device = util.require_cuda_device(device)
+        data = data.to(device=device, dtype=torch.float32).contiguous()
+        n = int(data.shape[0])
+        if metric == _metrics.COSINE:
+            data = _metrics.normalized_rows(data, metric)
+    if metric == _metrics.CORRELATION:
+        data = _metrics.normalized_rows(data, metric)
+    k = _clamp_k(k, n)
+    if approximate:
+        _ann.resolve_params(n, n_lists, n_probe)
+    if metric == _metrics.MANHATTAN:
+        idx, values = _metrics.manhattan_knn_lists(data, k)
+    elif csr is not None:
+        idx, values = _sparse_knn_lists(csr, k)
+    elif approximate and n >= _ann.MIN_ITEMS:
+        idx, values = _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
+    else:
+        idx, values = _dense_knn_lists(data, k)
+    if max_distance is None:
+        return idx, values, None
+    return idx, values, float(max_distance) * (1.0 if metric == _metrics.MANHATTAN else 2.0)
 
 
 def _clamp_k(k, n):

@@ -14,6 +14,7 @@ import torch
 from pymde_amd import _lib
 from pymde_amd import constraints
 from pymde_amd import graph as _graph
+from pymde_amd import metrics as _metrics
 from pymde_amd import preprocess
 from pymde_amd import problem
 from pymde_amd import util
@@ -32,14 +33,25 @@ class EdgeGraph(object):
         self.n_items = int(n_items)
 
 
-def distances(data, retain_fraction=1.0, seed=None, device=None):
-    """Euclidean distances between (a sample of) the pairs of rows of a data matrix
+def distances(data, retain_fraction=1.0, seed=None, device=None, metric="euclidean"):
+    """Distances (Euclidean by default) between (a sample of) the pairs of rows of a data matrix
     [ref: preprocess/data_matrix.py:11-88].  All ``n (n-1)/2`` pairs when ``retain_fraction >= 1``,
     otherwise a uniform sample of that fraction.
 
     ``data`` is a dense ``np.ndarray`` / ``torch.Tensor`` or a sparse data matrix (scipy sparse, any
     format, or a torch sparse COO / CSR tensor); sparse distances are summed over the union of the
-    two rows' columns (``mde_sparse_distances``), so near-duplicate rows come out near zero."""
+    two rows' columns (``mde_sparse_distances``), so near-duplicate rows come out near zero.
+
+    ``metric``: ``"euclidean"``, ``"cosine"``, ``"correlation"`` or ``"manhattan"`` (aliases ``"l2"``,
+    ``"l1"``, ``"cityblock"``), as ``scipy.spatial.distance`` defines them; the distances returned are in
+    the metric's own units.  Dense data: one pass over the two original rows per pair, sums in double
+    (``mde_pair_distances_metric``), so near-duplicate rows keep their small cosine / correlation
+    distances.  Sparse data: cosine scales the rows to unit length and halves the squared sparse distance;
+    correlation and Manhattan densify (an error if the dense copy does not fit).  A row without a
+    direction (all zero under cosine, constant under correlation) is an error."""
+    metric = _metrics.resolve(metric)
+    if metric != _metrics.EUCLIDEAN:
+        return _metric_distances(data, retain_fraction, seed, device, metric)
     if _sparse.is_sparse(data):
         csr = _sparse.to_device_csr(data, device)
         edges = _distance_edges(csr.n, retain_fraction, seed, csr.device)
@@ -66,6 +78,39 @@ def distances(data, retain_fraction=1.0, seed=None, device=None):
     return EdgeGraph(edges, delta, n)
 
 
+def _metric_distances(data, retain_fraction, seed, device, metric):
+    """``distances`` under a metric other than Euclidean."""
+    if _sparse.is_sparse(data):
+        csr = _sparse.to_device_csr(data, device)
+        if metric == _metrics.COSINE:
+            csr = _metrics.normalized_csr(csr)
+            edges = _distance_edges(csr.n, retain_fraction, seed, csr.device)
+            chord = torch.empty(edges.shape[0], dtype=torch.float32, device=csr.device)
+            with torch.cuda.device(csr.device):
+                _lib.check(_lib.load().mde_sparse_distances(
+                    csr.n, csr.n_features, csr.nnz, _lib.ptr(csr.indptr), _lib.ptr(csr.indices),
+                    _lib.ptr(csr.values), edges.shape[0], _lib.ptr(edges), _lib.ptr(chord),
+                    _lib.stream_ptr(csr.device)))
+            return EdgeGraph(edges, 0.5 * chord * chord, csr.n)      # |u - v|^2 = 2 (1 - cos) for unit rows
+        if not preprocess._densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
+            raise ValueError(
+                f"metric='{metric}' densifies sparse data, and the dense copy of this {csr.n} x "
+                f"{csr.n_features} matrix does not fit in the device memory allowed for it; "
+                "metric='cosine' and 'euclidean' have a sparse kernel")
+        data = csr.to_dense()
+    else:
+        if not isinstance(data, torch.Tensor):
+            data = torch.as_tensor(data)
+        if device is None:
+            device = data.device if data.is_cuda else util.get_default_device()
+        device = util.require_cuda_device(device)
+        data = data.to(device=device, dtype=torch.float32).contiguous()
+    _metrics.check_rows(data, metric)
+    n = int(data.shape[0])
+    edges = _distance_edges(n, retain_fraction, seed, data.device)
+    return EdgeGraph(edges, _metrics.pair_distances(data, edges, metric), n)
+
+
 def _distance_edges(n, retain_fraction, seed, device):
     """All pairs i < j when ``retain_fraction >= 1``, otherwise a uniform sample of that fraction."""
     all_edges = n * (n - 1) // 2
@@ -88,14 +133,19 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
-                       max_distances=5e7, device=None, verbose=False, seed=None):
-    """An MDE problem that preserves the pairwise Euclidean distances of a data matrix
+                       max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean"):
+    """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
     length.  ``data`` is a dense ``np.ndarray`` / ``torch.Tensor``, a sparse data matrix (scipy
     sparse or a torch sparse COO / CSR tensor -- a data matrix, not an adjacency matrix), or a
-    ``Graph``.  Call ``.embed()`` on the result."""
+    ``Graph``.  ``metric`` (data matrices only) as for ``distances``: the deviations are in the metric's
+    own units, and ``Standardized()`` rescales them as it does Euclidean ones.  Call ``.embed()`` on the
+    result."""
+    metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
+    if is_graph:
+        _metrics.check_graph(metric)
     if not is_graph and not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
         raise ValueError("`data` must be a np.ndarray/torch.Tensor/sparse data matrix, or a pymde_amd.Graph.")
     n_items = data.n_items if is_graph else int(data.shape[0])
@@ -108,7 +158,7 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
         graph = _graph.shortest_paths(data, retain_fraction=retain_fraction,
                                       seed=0 if seed is None else seed)
     else:
-        graph = distances(data, retain_fraction=retain_fraction, seed=seed, device=device)
+        graph = distances(data, retain_fraction=retain_fraction, seed=seed, device=device, metric=metric)
     edges, deviations = graph.edges, graph.distances
     if constraint is None:
         constraint = constraints.Centered()
@@ -125,7 +175,7 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
 def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p,
                        repulsive_penalty=penalties.Log, constraint=None, n_neighbors=None,
                        repulsive_fraction=None, max_distance=None, init="quadratic", device=None,
-                       verbose=False, seed=None, approximate_neighbors=False):
+                       verbose=False, seed=None, approximate_neighbors=False, metric="euclidean"):
     """An MDE problem that preserves the k-nearest-neighbour structure of a data matrix
     (rows = items) [ref: recipes.py:221-448]: k-NN graph (weights 1 / 2), optional spectral
     initialisation, uniformly sampled repulsive edges (weight -1), ``PushAndPull`` of the two
@@ -137,9 +187,17 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     ``approximate_neighbors`` (data matrices only): ``True`` builds the k-NN graph by the approximate
     inverted-file search of ``preprocess.k_nearest_neighbors(approximate=True)`` with its defaults, a dict
     ``{"n_lists": .., "n_probe": ..}`` sets those knobs; ``False`` (the default) keeps the exact search.
-    Recall depends on the data; ``verbose=True`` logs an estimate."""
+    Recall depends on the data; ``verbose=True`` logs an estimate.
+
+    ``metric`` (data matrices only): the distance in the original data under which neighbours are taken,
+    as for ``preprocess.k_nearest_neighbors`` -- ``"euclidean"``, ``"cosine"``, ``"correlation"`` or
+    ``"manhattan"``; ``max_distance`` is in its units.  The embedding side does not change."""
+    metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
+    if is_graph:
+        _metrics.check_graph(metric)
     knn_options = _approximate_options(approximate_neighbors)
+    _metrics.check_approximate(metric, bool(knn_options))
     if is_graph and knn_options:
         raise ValueError("approximate_neighbors applies to data matrices; a Graph has no approximate search")
     if not is_graph and not isinstance(data, torch.Tensor) and not _sparse.is_sparse(data):
@@ -176,6 +234,8 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
         if knn_options:
             knn_options.setdefault("seed", 0 if seed is None else seed)
             knn_options["verbose"] = verbose
+        if metric != _metrics.EUCLIDEAN:
+            knn_options["metric"] = metric
         edges, weights = preprocess.k_nearest_neighbors(data, k=n_neighbors, max_distance=max_distance,
                                                         device=device, **knn_options)
     if isinstance(constraint, constraints.Anchored):
@@ -236,11 +296,11 @@ def _approximate_options(approximate_neighbors):
 
 
 def laplacian_embedding(data, embedding_dim=2, n_neighbors=None, max_distance=None, init="quadratic",
-                        device=None, verbose=False, approximate_neighbors=False):
+                        device=None, verbose=False, approximate_neighbors=False, metric="euclidean"):
     """An MDE problem whose solution is a Laplacian embedding [ref: recipes.py:451-503]: the k-NN
     graph of ``preserve_neighbors`` with quadratic penalties, no repulsion and the standardization
-    constraint.  ``data`` and ``approximate_neighbors`` as for ``preserve_neighbors``."""
+    constraint.  ``data``, ``approximate_neighbors`` and ``metric`` as for ``preserve_neighbors``."""
     return preserve_neighbors(data, embedding_dim=embedding_dim, attractive_penalty=penalties.Quadratic,
                               repulsive_penalty=None, n_neighbors=n_neighbors, max_distance=max_distance,
                               init=init, device=device, verbose=verbose,
-                              approximate_neighbors=approximate_neighbors)
+                              approximate_neighbors=approximate_neighbors, metric=metric)
