@@ -264,6 +264,26 @@ int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_ou
             float* sqn_work, void* stream);
 /* out[r] = |data[r]|^2 for the rows of data [n, nf] (f32; the norms mde_knn forms internally). */
 int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* out, void* stream);
+/* Exact k nearest rows of a corpus C [n_c, nf] for every row of Q [n_q, nf] (both float32, row-major, on
+ * the device): the query-against-corpus form of mde_knn.  idx_out [n_q, k] int32 holds
+ * rows of C, -1 where n_c < k; d2_out [n_q, k] the squared Euclidean distances, clamped at 0.  Each row is
+ * ordered by (d2, index): ties go to the smaller corpus index.  Nothing is excluded as "self": a query equal
+ * to a corpus row lists it at distance 0.  1 <= k <= 64; n_q, n_c < 2^31.
+ * The grid is (query block of 64 rows, corpus slice): a workgroup scans only its slice (a whole number of
+ * 64-column tiles; the last slices may be shorter or empty) and writes its sorted partial list to scratch
+ * [slices, n_q, k]; a second kernel merges the lists of each row by (d2, index).  No atomics.  A distance
+ * does not depend on the slice that computed it, so the result is bit-identical for every slice count.
+ * slices == 1: the search writes the outputs directly (no list scratch, no merge launch); slices == 0:
+ * chosen from the device's CU count (1 when the query blocks alone fill the device, otherwise about four
+ * workgroups per CU with at least 16 tiles per slice); 0 <= slices <= 65535.
+ * work: caller-allocated scratch of mde_knn_cross_work_bytes(n_q, n_c, k, slices) bytes (the row norms of Q
+ * and C, then the partial lists when there is more than one slice); the call allocates nothing.
+ * Arguments are checked on the host before any launch: MDE_E_INVALID with a message.
+ * mde_knn_cross_work_bytes returns a negative MDE_E_* code for invalid arguments (and, with slices == 0,
+ * when no device can be asked for its CU count). */
+int64_t mde_knn_cross_work_bytes(int64_t n_q, int64_t n_c, int32_t k, int32_t slices);
+int mde_knn_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t k,
+                  int32_t slices, int32_t* idx_out, float* d2_out, void* work, void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

@@ -157,6 +157,240 @@ extern "C" int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* o
   return MDE_OK;
 }
 
+// ---------------------------------------------------------------- query against corpus
+// The tile scheme of k_knn on two matrices and a 2-D grid: workgroup (x, y) owns query rows
+// [64 x, 64 x + 64) and scans the corpus columns of slice y, [y * slice_cols, (y + 1) * slice_cols) cut at
+// n_c (slice_cols a multiple of 64; a slice past the end is empty and writes an empty list).  Its sorted
+// top-k goes to list y of the outputs, laid out [slices, n_q, k]: with one slice these are the final
+// outputs, otherwise scratch that k_knn_cross_merge folds.  Nothing is excluded as "self".  Columns are
+// offered in increasing index, so each list is ordered by (d2, index).
+__global__ __launch_bounds__(MDE_BLOCK) void k_knn_cross(int n_q, int n_c, int nf, int k, int64_t slice_cols,
+                                                         const float* __restrict__ Q, const float* __restrict__ C,
+                                                         const float* __restrict__ qn,
+                                                         const float* __restrict__ cn,
+                                                         int32_t* __restrict__ idx_out,
+                                                         float* __restrict__ d2_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* sA = lds;                           // [KNN_BM][KNN_KBP]
+  float* sB = sA + KNN_BM * KNN_KBP;         // [KNN_BN][KNN_KBP]
+  float* sD = sB + KNN_BN * KNN_KBP;         // [KNN_BM][KNN_BN + 1] squared distances of the tile
+  float* bestd = sD + KNN_BM * (KNN_BN + 1); // [KNN_BM][k]
+  int* besti = reinterpret_cast<int*>(bestd + KNN_BM * k);  // [KNN_BM][k]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wi = wave >> 1, wj = wave & 1;   // quadrant of the 64x64 tile
+  const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
+  const int64_t lo = (int64_t)blockIdx.y * slice_cols;
+  const int64_t c_lo = lo < n_c ? lo : n_c, c_hi = lo + slice_cols < n_c ? lo + slice_cols : n_c;
+  for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {
+    bestd[i] = 3.402823466e+38f;
+    besti[i] = -1;
+  }
+  float worst = 3.402823466e+38f;            // thread t < 64: current k-th best of row t
+  const int li = lane & 31, lk = lane >> 5;
+  for (int64_t col0 = c_lo; col0 < c_hi; col0 += KNN_BN) {
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
+    constexpr int STG = (KNN_BM * KNN_KB) / MDE_BLOCK;
+    float ra[STG], rb[STG];
+    auto fetch = [&](int k0) {
+#pragma unroll
+      for (int q = 0; q < STG; ++q) {
+        const int e = tid + q * MDE_BLOCK;
+        const int r = e >> 5, c = e & 31;
+        const int64_t gr = row0 + r, gc = col0 + r;
+        const int f = k0 + c;
+        // clamped addresses, zeroed afterwards (as in k_knn): every load stays inside Q / C
+        const int fc = f < nf ? f : nf - 1;
+        const float va = Q[(gr < n_q ? gr : n_q - 1) * nf + fc];
+        const float vb = C[(gc < n_c ? gc : n_c - 1) * nf + fc];
+        ra[q] = (gr < n_q && f < nf) ? va : 0.0f;
+        rb[q] = (gc < n_c && f < nf) ? vb : 0.0f;
+      }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < nf; k0 += KNN_KB) {
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < STG; ++q) {
+        const int e = tid + q * MDE_BLOCK;
+        const int r = e >> 5, c = e & 31;
+        sA[r * KNN_KBP + c] = ra[q];
+        sB[r * KNN_KBP + c] = rb[q];
+      }
+      __syncthreads();
+      if (k0 + KNN_KB < nf) fetch(k0 + KNN_KB);
+      const float* pa = sA + (wi * 32 + li) * KNN_KBP + lk;
+      const float* pb = sB + (wj * 32 + li) * KNN_KBP + lk;
+#pragma unroll
+      for (int kk = 0; kk < KNN_KB; kk += 2)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[kk], pb[kk], acc, 0, 0, 0);
+    }
+    // C/D map of the 32x32 tile: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int r = wi * 32 + (q & 3) + 8 * (q >> 2) + 4 * lk;
+      const int c = wj * 32 + li;
+      const int64_t gr = row0 + r, gc = col0 + c;
+      float d2 = 3.402823466e+38f;
+      if (gr < n_q && gc < n_c) d2 = fmaxf(qn[gr] + cn[gc] - 2.0f * acc[q], 0.0f);
+      sD[r * (KNN_BN + 1) + c] = d2;
+    }
+    __syncthreads();
+    if (tid < KNN_BM)
+      mde_topk_merge(sD + tid * (KNN_BN + 1), KNN_BN, (int)col0, k, bestd + tid * k, besti + tid * k, worst);
+  }
+  __syncthreads();
+  const int rows = n_q - row0 < KNN_BM ? (int)(n_q - row0) : KNN_BM;
+  const int64_t base = ((int64_t)blockIdx.y * n_q + row0) * k;   // the block's rows are contiguous in list y
+  for (int i = tid; i < rows * k; i += MDE_BLOCK) {
+    idx_out[base + i] = besti[i];
+    d2_out[base + i] = bestd[i];
+  }
+}
+
+// Folds the `slices` sorted lists of every query row ([slices, n_q, k], empty slots FLT_MAX / -1) into the
+// row's top-k by (d2, index).  A workgroup owns 64 query rows: their 64 k entries of one slice are
+// contiguous, are staged through LDS by all threads, and one thread per row merges them.
+__global__ __launch_bounds__(MDE_BLOCK) void k_knn_cross_merge(int n_q, int k, int slices,
+                                                               const float* __restrict__ pd,
+                                                               const int32_t* __restrict__ pi,
+                                                               int32_t* __restrict__ idx_out,
+                                                               float* __restrict__ d2_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* sd = lds;                                          // [KNN_BM][k] one slice's lists
+  int* si = reinterpret_cast<int*>(sd + KNN_BM * k);
+  float* bestd = reinterpret_cast<float*>(si + KNN_BM * k); // [KNN_BM][k]
+  int* besti = reinterpret_cast<int*>(bestd + KNN_BM * k);
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
+  const int rows = n_q - row0 < KNN_BM ? (int)(n_q - row0) : KNN_BM;
+  for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {
+    bestd[i] = 3.402823466e+38f;
+    besti[i] = -1;
+  }
+  float worst_d = 3.402823466e+38f;
+  int worst_i = -1;
+  for (int s = 0; s < slices; ++s) {
+    const int64_t base = ((int64_t)s * n_q + row0) * k;
+    __syncthreads();
+    for (int i = tid; i < rows * k; i += MDE_BLOCK) {
+      sd[i] = pd[base + i];
+      si[i] = pi[base + i];
+    }
+    __syncthreads();
+    if (tid < rows)
+      mde_topk_merge_id(sd + tid * k, si + tid * k, k, k, bestd + tid * k, besti + tid * k, worst_d, worst_i);
+  }
+  __syncthreads();
+  for (int i = tid; i < rows * k; i += MDE_BLOCK) {
+    idx_out[row0 * k + i] = besti[i];
+    d2_out[row0 * k + i] = bestd[i];
+  }
+}
+
+// The automatic slice count (slices == 0).  Rule: when the query blocks alone give every CU a workgroup
+// (query blocks >= CUs) the corpus is not split; otherwise it is split so that the grid holds about
+// CROSS_GRID_PER_CU workgroups per CU, but no finer than CROSS_MIN_TILES 64-column tiles per slice (a
+// slice must amortise its list's k entries of merge work and its start-up).  Both constants are
+// unmeasured choices until tools/cross_knn_scale.py has run on the device (profiles/r09_cross_knn.txt).
+#define CROSS_GRID_PER_CU 4
+#define CROSS_MIN_TILES 16
+#define CROSS_MAX_SLICES 65535   // gridDim.y
+static int cross_cu_count(int* cus) {
+  static int cached[64];         // per device ordinal; 0 = not asked yet
+  int dev = 0;
+  MDE_HIP(hipGetDevice(&dev));
+  const bool slot = dev >= 0 && dev < 64;
+  if (slot && cached[dev] > 0) {
+    *cus = cached[dev];
+    return MDE_OK;
+  }
+  hipDeviceProp_t prop;
+  MDE_HIP(hipGetDeviceProperties(&prop, dev));
+  *cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+  if (slot) cached[dev] = *cus;
+  return MDE_OK;
+}
+static int64_t cross_auto_slices(int64_t n_q, int64_t n_c, int cus) {
+  const int64_t qb = (n_q + KNN_BM - 1) / KNN_BM, tiles = (n_c + KNN_BN - 1) / KNN_BN;
+  if (qb >= cus) return 1;
+  int64_t s = ((int64_t)CROSS_GRID_PER_CU * cus + qb - 1) / qb;
+  if (s > tiles / CROSS_MIN_TILES) s = tiles / CROSS_MIN_TILES;
+  if (s > CROSS_MAX_SLICES) s = CROSS_MAX_SLICES;
+  return s < 1 ? 1 : s;
+}
+// slices as given, or the automatic count for 0; a negative MDE_E_* code on failure
+static int64_t cross_resolve_slices(int64_t n_q, int64_t n_c, int32_t slices) {
+  if (slices != 0) return slices;
+  int cus = 0;
+  const int rc = cross_cu_count(&cus);
+  if (rc != MDE_OK) return rc;
+  return cross_auto_slices(n_q, n_c, cus);
+}
+static bool cross_args_ok(int64_t n_q, int64_t n_c, int32_t k, int32_t slices) {
+  return n_q > 0 && n_c > 0 && k > 0 && k <= KNN_MAXK && slices >= 0 && slices <= CROSS_MAX_SLICES;
+}
+
+extern "C" int64_t mde_knn_cross_work_bytes(int64_t n_q, int64_t n_c, int32_t k, int32_t slices) {
+  if (!cross_args_ok(n_q, n_c, k, slices)) {
+    mde_set_error("mde_knn_cross_work_bytes: invalid arguments (1 <= k <= %d, 0 <= slices <= %d)", KNN_MAXK,
+                  CROSS_MAX_SLICES);
+    return MDE_E_INVALID;
+  }
+  const int64_t s = cross_resolve_slices(n_q, n_c, slices);
+  if (s < 0) return s;
+  int64_t words = n_q + n_c;                                    // the row norms of Q and C
+  if (s > 1) words += 2 * s * n_q * (int64_t)k;                 // partial lists: d2 and idx, [s, n_q, k] each
+  return 4 * words;
+}
+
+extern "C" int mde_knn_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t k,
+                             int32_t slices, int32_t* idx_out, float* d2_out, void* work, void* stream) {
+  if (!cross_args_ok(n_q, n_c, k, slices) || nf <= 0 || !Q || !C || !idx_out || !d2_out || !work) {
+    mde_set_error("mde_knn_cross: invalid arguments (1 <= k <= %d, 0 <= slices <= %d, n_q, n_c, nf >= 1)",
+                  KNN_MAXK, CROSS_MAX_SLICES);
+    return MDE_E_INVALID;
+  }
+  if (n_q >= ((int64_t)1 << 31) || n_c >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
+  const int64_t s = cross_resolve_slices(n_q, n_c, slices);
+  if (s < 0) return (int)s;
+  hipStream_t st = mde_stream(stream);
+  float* qn = static_cast<float*>(work);
+  float* cn = qn + n_q;
+  float* pd = cn + n_c;                                         // [s, n_q, k], used when s > 1
+  int32_t* pi = reinterpret_cast<int32_t*>(pd + s * n_q * (int64_t)k);
+  hipLaunchKernelGGL(k_row_sqnorm, dim3(mde_grid(n_q * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_q, nf, Q,
+                     qn);
+  MDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_row_sqnorm, dim3(mde_grid(n_c * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_c, nf, C,
+                     cn);
+  MDE_LAUNCH_CHECK();
+  const size_t lds = sizeof(float) * (size_t)(KNN_BM * KNN_KBP + KNN_BN * KNN_KBP + KNN_BM * (KNN_BN + 1)) +
+                     (size_t)KNN_BM * k * (sizeof(float) + sizeof(int));
+  const size_t lds_merge = (size_t)KNN_BM * k * 2 * (sizeof(float) + sizeof(int));
+  static bool attr = false;
+  if (!attr) {
+    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_cross),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_cross_merge),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    attr = true;
+  }
+  const int64_t tiles = (n_c + KNN_BN - 1) / KNN_BN;
+  const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;    // whole tiles; the last slices may be short or empty
+  const unsigned qb = (unsigned)((n_q + KNN_BM - 1) / KNN_BM);
+  hipLaunchKernelGGL(k_knn_cross, dim3(qb, (unsigned)s), dim3(MDE_BLOCK), lds, st, (int)n_q, (int)n_c, nf, k,
+                     slice_cols, Q, C, qn, cn, s > 1 ? pi : idx_out, s > 1 ? pd : d2_out);
+  MDE_LAUNCH_CHECK();
+  if (s > 1) {
+    hipLaunchKernelGGL(k_knn_cross_merge, dim3(qb), dim3(MDE_BLOCK), lds_merge, st, (int)n_q, k, (int)s, pd, pi,
+                       idx_out, d2_out);
+    MDE_LAUNCH_CHECK();
+  }
+  return MDE_OK;
+}
+
 // Directed neighbour lists -> edge list for mde_edges_count_unique: pairs_out[r * k + c] = (r, idx[r][c]).
 // Empty slots (idx < 0) and, when `val` is given, entries with val > max_value become the self pair
 // (r, r), which the edge counter drops [ref: data_matrix.py:147-175 -- neighbours beyond max_distance

@@ -263,6 +263,105 @@ def _dense_knn_lists(data, k):
     return idx, d2
 
 
+def _is_graph(data):
+    return hasattr(data, "edges") and hasattr(data, "n_items") and not isinstance(data, torch.Tensor)
+
+
+def _dense_rows_for_cross(data, device, what):
+    """The dense float32 [n, nf] copy on ``device`` of one argument of ``cross_nearest_neighbors``."""
+    if _sparse.is_sparse(data):
+        csr = _sparse.to_device_csr(data, device)
+        if not _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
+            raise ValueError(
+                f"cross_nearest_neighbors densifies sparse data, and the dense copy of the {csr.n} x "
+                f"{csr.n_features} `{what}` matrix does not fit in the device memory allowed for it")
+        return csr.to_dense()
+    if not isinstance(data, torch.Tensor):
+        data = torch.as_tensor(data)
+    if data.dim() != 2:
+        raise ValueError(f"`{what}` must be a matrix [n, n_features] (got shape {tuple(data.shape)})")
+    return data.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _cross_knn_lists(queries, data, k, slices=0):
+    """(idx [n_q, k] int32, d2 [n_q, k]) of ``mde_knn_cross``: for every row of the dense float32 ``queries``
+    its k nearest rows of the dense float32 ``data`` (same GPU), ordered by (d2, index); empty slots
+    (``data`` has fewer than k rows) hold -1 / FLT_MAX.  ``slices``: the corpus split, 0 = automatic."""
+    n_q, n_c, nf = int(queries.shape[0]), int(data.shape[0]), int(data.shape[1])
+    device = data.device
+    lib = _lib.load()
+    idx = torch.empty((n_q, k), dtype=torch.int32, device=device)
+    d2 = torch.empty((n_q, k), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        nbytes = int(lib.mde_knn_cross_work_bytes(n_q, n_c, k, slices))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.mde_knn_cross(n_q, n_c, nf, _lib.ptr(queries), _lib.ptr(data), k, slices, _lib.ptr(idx),
+                                     _lib.ptr(d2), _lib.ptr(work), _lib.stream_ptr(device)))
+    return idx, d2
+
+
+def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclidean", device=None):
+    """For every row of ``queries`` [n_q, n_features] its ``k`` nearest rows of ``data`` [n_c, n_features]:
+    the exact query-against-corpus search (``mde_knn_cross``).  The reference leaves
+    this search to the user; here it is what ``recipes.extend_embedding`` places new points with.
+
+    Returns ``(idx int64 [n_q, k], dist float32 [n_q, k])`` on the GPU, each row ascending; ties go to the
+    smaller row of ``data``.  ``dist`` is in the metric's own units (Euclidean: the distance, not its
+    square; cosine / correlation: ``1 - cos`` of the (centred) rows).  Nothing is excluded as "self": a
+    query that equals a row of ``data`` lists it at distance 0.  Slots beyond ``max_distance`` (in the
+    metric's units), and slots beyond the number of rows of ``data`` when ``k`` exceeds it, hold -1 / +inf.
+
+    ``queries`` and ``data`` are dense ``np.ndarray`` / ``torch.Tensor`` or sparse data matrices (scipy
+    sparse, torch sparse COO / CSR); sparse inputs are densified (an error if the dense copy does not fit
+    in the device memory allowed for it, ``_densify_sparse_knn``).  ``metric``: ``"euclidean"``,
+    ``"cosine"`` or ``"correlation"`` (and their aliases); cosine and correlation normalise the two matrices
+    separately and search the unit rows with the Euclidean kernel, and a row without a direction in either
+    matrix is an error.  There is no Manhattan cross kernel and no approximate cross search; a ``Graph``
+    is not a data matrix."""
+    metric = _metrics.resolve(metric)
+    if metric == _metrics.MANHATTAN:
+        raise ValueError("cross_nearest_neighbors has no Manhattan kernel; the metrics it serves are "
+                         "'euclidean', 'cosine' and 'correlation'")
+    if _is_graph(queries) or _is_graph(data):
+        raise ValueError("cross_nearest_neighbors searches data matrices; a Graph has no rows to search")
+    for name, m in (("queries", queries), ("data", data)):
+        if not hasattr(m, "shape") or len(m.shape) != 2:
+            raise ValueError(f"`{name}` must be a matrix [n, n_features]")
+    if int(queries.shape[1]) != int(data.shape[1]):
+        raise ValueError(f"`queries` has {int(queries.shape[1])} features and `data` has {int(data.shape[1])}; "
+                         "they must agree")
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    n_q, n_c = int(queries.shape[0]), int(data.shape[0])
+    if n_c < 1:
+        raise ValueError("`data` needs at least one row")
+    if device is None:
+        on_gpu = [m.device for m in (data, queries) if isinstance(m, torch.Tensor) and m.is_cuda]
+        device = on_gpu[0] if on_gpu else util.get_default_device()
+    device = util.require_cuda_device(device)
+    Q = _dense_rows_for_cross(queries, device, "queries")
+    C = _dense_rows_for_cross(data, device, "data")
+    if metric != _metrics.EUCLIDEAN:
+        if n_q:
+            Q = _metrics.normalized_rows(Q, metric)
+        C = _metrics.normalized_rows(C, metric)
+    if n_q == 0:
+        return (torch.empty((0, k), dtype=torch.int64, device=device),
+                torch.empty((0, k), dtype=torch.float32, device=device))
+    idx32, d2 = _cross_knn_lists(Q, C, k)
+    dist = d2.sqrt() if metric == _metrics.EUCLIDEAN else 0.5 * d2
+    empty = idx32 < 0
+    if max_distance is not None:
+        empty = empty | ~(dist <= float(max_distance))
+    idx = idx32.to(torch.int64)
+    idx[empty] = -1
+    dist[empty] = float("inf")
+    return idx, dist
+
+
 def _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose):
     """Directed neighbour lists of a dense float32 [n, nf] on the GPU by the inverted-file search."""
     n_lists, n_probe = _ann.resolve_params(int(data.shape[0]), n_lists, n_probe)

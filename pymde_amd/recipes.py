@@ -278,6 +278,131 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     return mde
 
 
+def _sample_new_item_edges(n_old, n_new, count, exclude, generator, device):
+    """Up to ``count`` distinct edges (i < j, sorted by (i, j)), each pairing a uniformly drawn new item
+    (index >= n_old) with a uniformly drawn other item, old or new; none of them in ``exclude`` [p, 2]
+    (i < j).  Drawn directly among the pairs that touch a new item, by rejection of the rare repeats."""
+    n = n_old + n_new
+    available = n_new * n_old + n_new * (n_new - 1) // 2 - int(exclude.shape[0])
+    count = min(int(count), available)
+    if count <= 0:
+        return torch.empty((0, 2), dtype=torch.int64, device=device)
+    exclude_keys = exclude[:, 0] * n + exclude[:, 1]
+    found = torch.empty((0, 2), dtype=torch.int64, device=device)
+    for _ in range(64):
+        missing = count - int(found.shape[0])
+        if missing <= 0:
+            break
+        draws = 2 * missing + 1024
+        i = torch.randint(n_old, n, (draws,), generator=generator, device=device)
+        j = torch.randint(0, n - 1, (draws,), generator=generator, device=device)
+        j = j + (j >= i).to(torch.int64)                           # uniform over the items other than i
+        lo, hi = torch.minimum(i, j), torch.maximum(i, j)
+        keep = ~torch.isin(lo * n + hi, exclude_keys)
+        found = preprocess.deduplicate_edges(torch.cat([found, torch.stack([lo[keep], hi[keep]], 1)]), n_items=n)
+    if found.shape[0] > count:
+        # the distinct draws are exchangeable: a uniform subset of them, kept in sorted order
+        pick = torch.randperm(found.shape[0], generator=generator, device=device)[:count]
+        found = found[torch.sort(pick).values]
+    return found.contiguous()
+
+
+def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repulsive_penalty=penalties.Log,
+                     n_neighbors=None, repulsive_fraction=None, max_distance=None, metric="euclidean",
+                     device=None, verbose=False, seed=None):
+    """An MDE problem that places new points into an existing embedding: ``data`` [n_old, n_features] are
+    the rows already embedded, ``X`` [n_old, m] their embedding (the embedding dimension is taken from it;
+    it is used as float32), ``new_data`` [n_new, n_features] the rows to add.  The reference documents
+    this as an ``Anchored`` problem over old and new items and leaves the neighbour search to the user;
+    here the search is ``preprocess.cross_nearest_neighbors`` (every stage on the GPU).
+
+    The result is an ``MDE`` over ``n_old + n_new`` items, old items first, constrained by
+    ``Anchored(anchors=arange(n_old), values=X)``: after ``.embed()`` the rows ``[:n_old]`` of the embedding
+    equal ``X`` bit for bit and the rows ``[n_old:]`` are the new points.
+
+    Attractive edges (weight 1): one edge between new item ``n_old + q`` and each of the ``n_neighbors``
+    rows of ``data`` nearest to ``new_data[q]`` under ``metric`` (``"euclidean"``, ``"cosine"`` or
+    ``"correlation"``; not Manhattan) and within ``max_distance`` (in the metric's units).  New points take
+    their neighbours among the old rows only -- never among each other -- and the search is exact (there is
+    no approximate cross search).  ``n_neighbors`` defaults as in ``preserve_neighbors``, computed from
+    ``n_old``.  A new point with no neighbour within ``max_distance`` is an error: it would have repulsion
+    only.  Repulsive edges (weight -1; none when ``repulsive_penalty`` is None):
+    ``int(repulsive_fraction * n_attractive)`` of them (fraction 1 by default), each pairing a uniformly
+    drawn new item with a uniformly drawn other item, old or new, with no self pair, no attractive pair and
+    no repeat; the same ``seed`` gives the same edges.  Edges are stored with the smaller index first.
+
+    The solve starts from ``X`` for the old rows and, for each new row, from the mean of its neighbours'
+    rows of ``X`` (perturbed by 1e-4 when that leaves an edge of length zero).  An embedding that was
+    ``Standardized`` does not stay standardized once new rows are added."""
+    metric = _metrics.resolve(metric)
+    if metric == _metrics.MANHATTAN:
+        raise ValueError("extend_embedding has no Manhattan neighbour search; the metrics it serves are "
+                         "'euclidean', 'cosine' and 'correlation'")
+    for name, m in (("data", data), ("new_data", new_data)):
+        if isinstance(m, _graph.Graph) or not hasattr(m, "shape") or len(m.shape) != 2:
+            raise ValueError(f"`{name}` must be a data matrix (np.ndarray / torch.Tensor / sparse matrix)")
+    if not isinstance(X, torch.Tensor):
+        X = torch.as_tensor(X)
+    n_old, n_new = int(data.shape[0]), int(new_data.shape[0])
+    if X.dim() != 2 or int(X.shape[0]) != n_old:
+        raise ValueError(f"`X` must hold one embedding vector per row of `data` ({n_old}); got shape "
+                         f"{tuple(X.shape)}")
+    if n_new < 1:
+        raise ValueError("`new_data` needs at least one row")
+    if device is None:
+        on_gpu = [t.device for t in (X, data, new_data) if isinstance(t, torch.Tensor) and t.is_cuda]
+        device = on_gpu[0] if on_gpu else util.get_default_device()
+    device = util.require_cuda_device(device)
+    X = X.detach().to(device=device, dtype=torch.float32).contiguous()
+    n, m = n_old + n_new, int(X.shape[1])
+    if n_neighbors is None:
+        n_neighbors = int(max(min(15, (n_old * (n_old - 1) / 2) * 0.01 / n_old), 5))
+    if n_neighbors > n_old:
+        problem.LOGGER.warning(f"Requested n_neighbors {n_neighbors} > number of embedded items {n_old}. "
+                               f"Setting n_neighbors to {n_old}")
+        n_neighbors = n_old
+    if verbose:
+        problem.LOGGER.info(f"Computing the {n_neighbors} nearest embedded rows of {n_new} new rows among "
+                            f"{n_old}, with max_distance={max_distance}")
+    idx, _ = preprocess.cross_nearest_neighbors(new_data, data, n_neighbors, max_distance=max_distance,
+                                                metric=metric, device=device)
+    listed = idx >= 0
+    n_alone = int((~listed.any(1)).sum())
+    if n_alone:
+        raise ValueError(f"{n_alone} of the {n_new} new points have no neighbour within max_distance="
+                         f"{max_distance}: they would have repulsive edges only")
+    new_items = torch.arange(n_old, n, device=device).unsqueeze(1).expand_as(idx)
+    edges = torch.stack([idx[listed], new_items[listed]], 1)       # (old, new): the smaller index first
+    weights = torch.ones(edges.shape[0], dtype=torch.float32, device=device)
+    generator = torch.Generator(device=device)
+    generator.manual_seed(int(util.np_rng().integers(0, 2 ** 63 - 1)) if seed is None else int(seed))
+    if repulsive_penalty is not None:
+        if repulsive_fraction is None:
+            repulsive_fraction = 1
+        n_repulsive = int(repulsive_fraction * edges.shape[0])
+        if verbose:
+            problem.LOGGER.info(f"Sampling {n_repulsive} repulsive edges at the new items")
+        negative_edges = _sample_new_item_edges(n_old, n_new, n_repulsive, edges, generator, device)
+        edges = torch.cat([edges, negative_edges])
+        weights = torch.cat([weights, -torch.ones(negative_edges.shape[0], dtype=torch.float32, device=device)])
+        f = penalties.PushAndPull(weights, attractive_penalty=attractive_penalty,
+                                  repulsive_penalty=repulsive_penalty)
+    else:
+        f = attractive_penalty(weights)
+    constraint = constraints.Anchored(anchors=torch.arange(n_old, device=device), values=X)
+    mde = problem.MDE(n_items=n, embedding_dim=m, edges=edges, distortion_function=f, constraint=constraint,
+                      device=device)
+    if verbose:
+        problem.LOGGER.info("Starting the new rows at the mean of their neighbours' embedding vectors")
+    neighbours = X[idx.clamp(min=0)] * listed.unsqueeze(2)                       # [n_new, k, m]
+    X_new = neighbours.sum(1) / listed.sum(1, keepdim=True)
+    # overlapping points make the average distortion non-differentiable: perturb the new rows apart
+    if bool((mde.distances(torch.cat([X, X_new])) == 0).any()):
+        X_new = X_new + 1e-4 * torch.randn(X_new.shape, generator=generator, device=device, dtype=X_new.dtype)
+    mde._X_init = torch.cat([X, X_new]).contiguous()
+    return mde
+
+
 def _approximate_options(approximate_neighbors):
     """Keywords of ``preprocess.k_nearest_neighbors`` for a recipe's ``approximate_neighbors`` value:
     False -> {} (the exact search), True -> approximate with the defaults, a dict -> approximate with
