@@ -264,6 +264,17 @@ int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_ou
             float* sqn_work, void* stream);
 /* out[r] = |data[r]|^2 for the rows of data [n, nf] (f32; the norms mde_knn forms internally). */
 int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* out, void* stream);
+/* Column statistics of data [n, nf] for the translation that precedes a Euclidean search:
+ * stats_out double [2, nf] on the device = (column means, population variances), summed in double without
+ * floating-point atomics (the same on every run); bad_row_out int32 [1] on the device = the first row that
+ * holds a NaN or an infinity, INT32_MAX when there is none (the statistics mean nothing otherwise).  work:
+ * mde_col_stats_work_bytes(n, nf) bytes of scratch (at most 64 MiB); the call allocates nothing.  stats_out
+ * and work both NULL: the non-finite scan alone.  ASYNC. */
+int64_t mde_col_stats_work_bytes(int64_t n, int32_t nf);
+int mde_col_stats(int64_t n, int32_t nf, const float* data, double* stats_out, int32_t* bad_row_out, void* work,
+                  void* stream);
+/* out [n, nf] = data - mu, mu double [nf] on the device: subtracted in double, rounded to f32 once.  ASYNC. */
+int mde_rows_subtract(int64_t n, int32_t nf, const float* data, const double* mu, float* out, void* stream);
 /* Exact k nearest rows of a corpus C [n_c, nf] for every row of Q [n_q, nf] (both float32, row-major, on
  * the device): the query-against-corpus form of mde_knn.  idx_out [n_q, k] int32 holds
  * rows of C, -1 where n_c < k; d2_out [n_q, k] the squared Euclidean distances, clamped at 0.  Each row is

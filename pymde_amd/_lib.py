@@ -77,6 +77,9 @@ SYMBOLS = {
     "mde_edges_count_unique": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_knn": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_row_sqnorm": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "mde_col_stats_work_bytes": (c_i64, [c_i64, c_i32]),
+    "mde_col_stats": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_rows_subtract": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_knn_cross_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "mde_knn_cross": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_ann_search": (c_i32, [c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,

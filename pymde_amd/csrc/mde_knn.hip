@@ -157,6 +157,136 @@ extern "C" int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* o
   return MDE_OK;
 }
 
+// ---------------------------------------------------------------- translation to the column means
+// |x|^2 + |y|^2 - 2 x.y in f32 is accurate to ~1e-7 of |x|^2 + |y|^2, so a common offset of the rows that
+// dominates their spread swallows the distances.  Euclidean distance is translation invariant: the callers
+// search the rows minus their column means instead.  Three kernels, all O(n nf) beside the O(n^2 nf) search.
+//
+// k_col_stats: workgroup (x, y) owns columns [64 x, 64 x + 64) and the rows 4 y + (tid >> 6) + 4 chunks i: a
+// wave reads 64 consecutive floats of one row.  Sum and sum of squares per column in double (the product of
+// two floats is exact there), the four row lanes folded through LDS in a fixed order and written to
+// part[y][0 / 1][c]; k_col_stats_fold adds the chunks in order -- no floating-point atomics, so the means are
+// the same on every run.  The smallest index of a row that holds a NaN or an infinity is min-reduced into
+// *bad_row (an integer atomic: order-free).  part may be NULL: the non-finite scan alone.
+#define COLS_BX 64
+#define COLS_MAX_CHUNKS 512
+#define COLS_MAX_PARTIALS ((int64_t)1 << 22)   // chunks * nf: at most 64 MiB of partials
+static int col_stats_chunks(int64_t n, int32_t nf) {
+  int64_t c = (n + 63) / 64;
+  if (c > COLS_MAX_CHUNKS) c = COLS_MAX_CHUNKS;
+  if (c > COLS_MAX_PARTIALS / nf) c = COLS_MAX_PARTIALS / nf;
+  return c < 1 ? 1 : (int)c;
+}
+
+__global__ __launch_bounds__(MDE_BLOCK) void k_col_stats(int64_t n, int nf, const float* __restrict__ X,
+                                                         double* __restrict__ part, int* __restrict__ bad_row) {
+  static_assert(MDE_BLOCK == 4 * COLS_BX, "k_col_stats: four row lanes of 64 columns");
+  __shared__ double sh[3][2][COLS_BX];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int c = blockIdx.x * COLS_BX + cx;
+  double s = 0.0, q = 0.0;
+  int bad = 0x7fffffff;
+  if (c < nf)
+    for (int64_t r = (int64_t)blockIdx.y * 4 + ry; r < n; r += (int64_t)gridDim.y * 4) {
+      const float v = X[r * nf + c];
+      s += (double)v;
+      q += (double)v * (double)v;
+      if (!(fabsf(v) <= 3.402823466e+38f) && (int)r < bad) bad = (int)r;
+    }
+  if (ry > 0) {
+    sh[ry - 1][0][cx] = s;
+    sh[ry - 1][1][cx] = q;
+  }
+  __syncthreads();
+  if (part && ry == 0 && c < nf) {
+    for (int i = 0; i < 3; ++i) {
+      s += sh[i][0][cx];
+      q += sh[i][1][cx];
+    }
+    part[((int64_t)blockIdx.y * 2 + 0) * nf + c] = s;
+    part[((int64_t)blockIdx.y * 2 + 1) * nf + c] = q;
+  }
+  if (bad != 0x7fffffff) atomicMin(bad_row, bad);
+}
+
+// stats[c] = mean of column c, stats[nf + c] = its variance (population; clamped at 0), both in double
+__global__ __launch_bounds__(MDE_BLOCK) void k_col_stats_fold(int64_t n, int nf, int chunks,
+                                                              const double* __restrict__ part,
+                                                              double* __restrict__ stats) {
+  const int c = blockIdx.x * MDE_BLOCK + threadIdx.x;
+  if (c >= nf) return;
+  double s = 0.0, q = 0.0;
+  for (int y = 0; y < chunks; ++y) {
+    s += part[((int64_t)y * 2 + 0) * nf + c];
+    q += part[((int64_t)y * 2 + 1) * nf + c];
+  }
+  const double mean = s / (double)n, var = q / (double)n - mean * mean;
+  stats[c] = mean;
+  stats[nf + c] = var > 0.0 ? var : 0.0;
+}
+
+__global__ void k_bad_row_init(int* bad_row) { *bad_row = 0x7fffffff; }
+
+// out[r][c] = x[r][c] - mu[c], subtracted in double and rounded once (one wave per row, as k_row_sqnorm)
+__global__ __launch_bounds__(MDE_BLOCK) void k_rows_subtract(int64_t n, int nf, const float* __restrict__ X,
+                                                             const double* __restrict__ mu,
+                                                             float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = ((int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * MDE_BLOCK) >> 6;
+  for (int64_t r = w0; r < n; r += nw)
+    for (int c = lane; c < nf; c += 64) out[r * nf + c] = (float)((double)X[r * nf + c] - mu[c]);
+}
+
+extern "C" int64_t mde_col_stats_work_bytes(int64_t n, int32_t nf) {
+  if (n <= 0 || nf <= 0) {
+    mde_set_error("mde_col_stats_work_bytes: invalid arguments (n >= 1, nf >= 1)");
+    return MDE_E_INVALID;
+  }
+  return (int64_t)sizeof(double) * 2 * col_stats_chunks(n, nf) * nf;
+}
+
+// stats_out: double [2, nf] on the device = (column means, column variances); bad_row_out: int32 [1] on the
+// device = the first row that holds a NaN or an infinity (INT32_MAX when there is none; the statistics mean
+// nothing then); work: mde_col_stats_work_bytes(n, nf) bytes of scratch.  stats_out and work both NULL: the
+// non-finite scan alone (one pass, no partials, no fold).
+extern "C" int mde_col_stats(int64_t n, int32_t nf, const float* data, double* stats_out, int32_t* bad_row_out,
+                             void* work, void* stream) {
+  if (n <= 0 || nf <= 0 || !data || !bad_row_out || (stats_out == nullptr) != (work == nullptr)) {
+    mde_set_error("mde_col_stats: invalid arguments (n >= 1, nf >= 1, non-null data / bad_row_out; stats_out and "
+                  "work both given or both NULL)");
+    return MDE_E_INVALID;
+  }
+  if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
+  hipStream_t st = mde_stream(stream);
+  const int chunks = col_stats_chunks(n, nf);
+  double* part = static_cast<double*>(work);
+  hipLaunchKernelGGL(k_bad_row_init, dim3(1), dim3(1), 0, st, bad_row_out);
+  MDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_col_stats, dim3((unsigned)((nf + COLS_BX - 1) / COLS_BX), (unsigned)chunks), dim3(MDE_BLOCK), 0,
+                     st, n, nf, data, part, bad_row_out);
+  MDE_LAUNCH_CHECK();
+  if (!stats_out) return MDE_OK;
+  hipLaunchKernelGGL(k_col_stats_fold, dim3((unsigned)((nf + MDE_BLOCK - 1) / MDE_BLOCK)), dim3(MDE_BLOCK), 0, st, n,
+                     nf, chunks, part, stats_out);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
+}
+
+// out [n, nf] = data - mu (mu: double [nf] on the device), rounded to f32 once.
+extern "C" int mde_rows_subtract(int64_t n, int32_t nf, const float* data, const double* mu, float* out,
+                                 void* stream) {
+  if (n <= 0 || nf <= 0 || !data || !mu || !out) {
+    mde_set_error("mde_rows_subtract: invalid arguments (n >= 1, nf >= 1, non-null data / mu / out)");
+    return MDE_E_INVALID;
+  }
+  if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
+  hipLaunchKernelGGL(k_rows_subtract, dim3(mde_grid(n * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, mde_stream(stream),
+                     n, nf, data, mu, out);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
+}
+
 // ---------------------------------------------------------------- query against corpus
 // The tile scheme of k_knn on two matrices and a 2-D grid: workgroup (x, y) owns query rows
 // [64 x, 64 x + 64) and scans the corpus columns of slice y, [y * slice_cols, (y + 1) * slice_cols) cut at

@@ -116,6 +116,16 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     approximate (pynndescent) above; this search is exact at every size unless ``approximate=True``.
     Self matches are excluded by index, so duplicated rows become ordinary zero-distance neighbours.
 
+    The kernels form ``|x|^2 + |y|^2 - 2 x.y`` in float32, which errs by ~1e-7 of ``|x|^2 + |y|^2``.  When
+    the common offset of the rows dominates their spread (``|column means|^2`` above the summed column
+    variance, both in double) the Euclidean search -- exact, approximate, densified sparse -- runs on a
+    float32 copy of the rows minus their column means (each rounded to a power-of-two grid no coarser than the
+    column's standard deviation, so integer data stay exact; ``4 n n_features`` bytes beside the data; DESIGN
+    section 6); data near the origin are searched as given.  The exact sparse kernel cannot subtract a dense
+    vector and keep its sparsity: a sparse matrix whose dense copy does not fit is searched untranslated and
+    keeps the float32 error relative to its own norms.  A row that holds NaN or infinity is a ``ValueError``
+    naming the row, as in the reference (sklearn's ``check_array``).
+
     ``approximate=True`` searches data matrices of at least 10 000 rows by an inverted file on the GPU
     (``pymde_amd.ann``, ``csrc/mde_ann.hip``): k-means (``seed``) splits the rows into ``n_lists`` lists
     (default round(sqrt(n))), and each row is compared with the rows of the ``n_probe`` lists whose
@@ -164,10 +174,11 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
                     f"approximate=True densifies sparse data, and the dense copy of this {csr.n} x "
                     f"{csr.n_features} matrix does not fit in the device memory allowed for it; "
                     "use approximate=False (the exact sparse kernel)")
-            idx, d2 = _approximate_knn_lists(csr.to_dense(), k, n_lists, n_probe, seed, verbose)
+            idx, d2 = _euclidean_knn_lists(csr.to_dense(), k, True, n_lists, n_probe, seed, verbose)
         elif _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
-            idx, d2 = _dense_knn_lists(csr.to_dense(), k)
+            idx, d2 = _euclidean_knn_lists(csr.to_dense(), k)
         else:
+            _check_finite_csr(csr)
             idx, d2 = _sparse_knn_lists(csr, k)
         max_d2 = None if max_distance is None else float(max_distance) ** 2
         return _neighbor_lists_to_graph(csr.n, k, idx, d2, max_d2, csr.device)
@@ -181,10 +192,7 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     k = _clamp_k(k, n)
     if approximate:
         _ann.resolve_params(n, n_lists, n_probe)      # the same argument checks at every size
-    if approximate and n >= _ann.MIN_ITEMS:
-        idx, d2 = _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
-    else:
-        idx, d2 = _dense_knn_lists(data, k)
+    idx, d2 = _euclidean_knn_lists(data, k, approximate, n_lists, n_probe, seed, verbose)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
     return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
 
@@ -249,8 +257,31 @@ def _clamp_k(k, n):
     return k
 
 
+def _euclidean_knn_lists(data, k, approximate=False, n_lists=None, n_probe=None, seed=0, verbose=False):
+    """Directed Euclidean neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the GPU:
+    what ``k_nearest_neighbors`` calls for Euclidean data.  The search -- exact, or the inverted file with its
+    recall estimate when ``approximate`` and n >= ``ann.MIN_ITEMS`` -- runs on the rows minus their float64
+    column means when the offset of the data dominates its spread (``metrics.translated_rows``, DESIGN
+    section 6), on ``data`` itself otherwise.  ``ValueError`` for a row that holds NaN or infinity, before
+    any list is produced."""
+    data, _ = _metrics.translated_rows(data)
+    if approximate and int(data.shape[0]) >= _ann.MIN_ITEMS:
+        return _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
+    return _dense_knn_lists(data, k)
+
+
+def _check_finite_csr(csr):
+    """``ValueError`` naming the first row of a ``sparse.DeviceCSR`` that stores a NaN or an infinity."""
+    bad = ~torch.isfinite(csr.values)
+    if bool(bad.any()):
+        entry = bad.nonzero()[0]
+        row = int(torch.searchsorted(csr.indptr, entry, right=True).item()) - 1
+        _metrics.raise_non_finite(row, "the data matrix")
+
+
 def _dense_knn_lists(data, k):
-    """Directed neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the GPU."""
+    """Directed neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the GPU by
+    ``mde_knn`` on the rows as given (``_euclidean_knn_lists`` translates them first where that matters)."""
     n, nf = int(data.shape[0]), int(data.shape[1])
     device = data.device
     lib = _lib.load()
@@ -281,6 +312,19 @@ def _dense_rows_for_cross(data, device, what):
     if data.dim() != 2:
         raise ValueError(f"`{what}` must be a matrix [n, n_features] (got shape {tuple(data.shape)})")
     return data.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _translated_pair(queries, data):
+    """The two dense float32 matrices a Euclidean cross search runs on: both minus the float64 column means
+    of the corpus ``data`` when its offset dominates its spread (one vector for both, so every distance is
+    kept; ``metrics.translated_rows``), the matrices themselves otherwise.  ``ValueError`` naming the argument
+    and the row when either holds a NaN or an infinity."""
+    if int(queries.shape[0]):
+        _metrics.check_finite(queries, "`queries`")
+    data, mu = _metrics.translated_rows(data, "`data`")
+    if mu is not None and int(queries.shape[0]):
+        queries = _metrics.subtract_columns(queries, mu)
+    return queries, data
 
 
 def _cross_knn_lists(queries, data, k, slices=0):
@@ -318,7 +362,9 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
     in the device memory allowed for it, ``_densify_sparse_knn``).  ``metric``: ``"euclidean"``,
     ``"cosine"`` or ``"correlation"`` (and their aliases); cosine and correlation normalise the two matrices
     separately and search the unit rows with the Euclidean kernel, and a row without a direction in either
-    matrix is an error.  There is no Manhattan cross kernel and no approximate cross search; a ``Graph``
+    matrix is an error.  The Euclidean search runs on both matrices minus the column means of ``data`` when
+    that offset dominates the spread of ``data`` (as in ``k_nearest_neighbors``), and a row of either matrix
+    that holds NaN or infinity is a ``ValueError`` naming the argument and the row.  There is no Manhattan cross kernel and no approximate cross search; a ``Graph``
     is not a data matrix."""
     metric = _metrics.resolve(metric)
     if metric == _metrics.MANHATTAN:
@@ -348,6 +394,8 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
         if n_q:
             Q = _metrics.normalized_rows(Q, metric)
         C = _metrics.normalized_rows(C, metric)
+    else:
+        Q, C = _translated_pair(Q, C)
     if n_q == 0:
         return (torch.empty((0, k), dtype=torch.int64, device=device),
                 torch.empty((0, k), dtype=torch.float32, device=device))
