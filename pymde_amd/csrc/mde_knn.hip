@@ -1,23 +1,9 @@
 // mde_knn.hip -- exact k-nearest-neighbour search on a data matrix.
 //   [ref: pymde/preprocess/data_matrix.py:91-178 k_nearest_neighbors -- sklearn brute force for
 //    n < 10 000, pynndescent (approximate, un-vendored) above; here: exact at every size]
-// Squared distances are formed as |x|^2 + |y|^2 - 2 x.y with the Gram tile x.y on the f32 matrix
-// cores (v_mfma_f32_32x32x2_f32, exact f32): a 256-thread workgroup owns 64 query rows and walks
-// the candidates 64 at a time; each wave accumulates one 32x32 quadrant of the 64x64 tile over the
-// features, staged through LDS in 32-wide chunks (rows padded to 33 floats: conflict-free operand
-// reads; the next chunk's global loads overlap the current chunk's MFMAs).  The tile of squared distances is parked in LDS and one thread per query row merges its
-// 64 candidates into the row's sorted top-k list (insertion only when a candidate beats the current
-// k-th best, which becomes rare quickly).  Self matches are excluded by index.
-#include "mde_common.h"
-#include "mde_topk.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define KNN_BM 64
-#define KNN_BN 64
-#define KNN_KB 32
-#define KNN_KBP 33
-#define KNN_MAXK 64
+// The search itself is k_knn_cross<true> below: the 64x64 Gram tile of mde_knn_tile.h with the data matrix on
+// both sides, one slice, and self matches excluded by index.
+#include "mde_knn_tile.h"
 
 __global__ __launch_bounds__(MDE_BLOCK) void k_row_sqnorm(int64_t n, int nf, const float* __restrict__ X,
                                                           float* __restrict__ out) {
@@ -35,119 +21,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_row_sqnorm(int64_t n, int nf, con
   }
 }
 
-__global__ __launch_bounds__(MDE_BLOCK) void k_knn(int n, int nf, int k, const float* __restrict__ X,
-                                                   const float* __restrict__ sqn,
-                                                   int32_t* __restrict__ idx_out,
-                                                   float* __restrict__ d2_out) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* sA = lds;                           // [KNN_BM][KNN_KBP]
-  float* sB = sA + KNN_BM * KNN_KBP;         // [KNN_BN][KNN_KBP]
-  float* sD = sB + KNN_BN * KNN_KBP;         // [KNN_BM][KNN_BN + 1] squared distances of the tile
-  float* bestd = sD + KNN_BM * (KNN_BN + 1); // [KNN_BM][k]
-  int* besti = reinterpret_cast<int*>(bestd + KNN_BM * k);  // [KNN_BM][k]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wj = wave & 1;   // quadrant of the 64x64 tile
-  const int row0 = blockIdx.x * KNN_BM;
-  for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {
-    bestd[i] = 3.402823466e+38f;
-    besti[i] = -1;
-  }
-  float worst = 3.402823466e+38f;            // thread t < 64: current k-th best of row t
-  const int li = lane & 31, lk = lane >> 5;
-  for (int col0 = 0; col0 < n; col0 += KNN_BN) {
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-    // feature chunks of KNN_KB: the next chunk's global loads are issued before the MFMAs of the
-    // current one and committed to LDS after them (register double buffering), so the matrix
-    // cores do not wait for the staging latency
-    constexpr int STG = (KNN_BM * KNN_KB) / MDE_BLOCK;
-    float ra[STG], rb[STG];
-    auto fetch = [&](int k0) {
-#pragma unroll
-      for (int q = 0; q < STG; ++q) {
-        const int e = tid + q * MDE_BLOCK;
-        const int r = e >> 5, c = e & 31;
-        const int gr = row0 + r, gc = col0 + r, f = k0 + c;
-        // plain loads from clamped addresses, zeroed afterwards: a predicated load is a branch around
-        // it and the sixteen loads of a chunk would go out one memory latency after the other
-        const int fc = f < nf ? f : nf - 1;
-        const float va = X[(int64_t)(gr < n ? gr : n - 1) * nf + fc];
-        const float vb = X[(int64_t)(gc < n ? gc : n - 1) * nf + fc];
-        ra[q] = (gr < n && f < nf) ? va : 0.0f;
-        rb[q] = (gc < n && f < nf) ? vb : 0.0f;
-      }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < nf; k0 += KNN_KB) {
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < STG; ++q) {
-        const int e = tid + q * MDE_BLOCK;
-        const int r = e >> 5, c = e & 31;
-        sA[r * KNN_KBP + c] = ra[q];
-        sB[r * KNN_KBP + c] = rb[q];
-      }
-      __syncthreads();
-      if (k0 + KNN_KB < nf) fetch(k0 + KNN_KB);
-      const float* pa = sA + (wi * 32 + li) * KNN_KBP + lk;
-      const float* pb = sB + (wj * 32 + li) * KNN_KBP + lk;
-#pragma unroll
-      for (int kk = 0; kk < KNN_KB; kk += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[kk], pb[kk], acc, 0, 0, 0);
-    }
-    // C/D map of the 32x32 tile: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int r = wi * 32 + (q & 3) + 8 * (q >> 2) + 4 * lk;
-      const int c = wj * 32 + li;
-      const int gr = row0 + r, gc = col0 + c;
-      float d2 = 3.402823466e+38f;
-      if (gr < n && gc < n && gr != gc) d2 = fmaxf(sqn[gr] + sqn[gc] - 2.0f * acc[q], 0.0f);
-      sD[r * (KNN_BN + 1) + c] = d2;
-    }
-    __syncthreads();
-    if (tid < KNN_BM)
-      mde_topk_merge(sD + tid * (KNN_BN + 1), KNN_BN, col0, k, bestd + tid * k, besti + tid * k, worst);
-  }
-  __syncthreads();
-  for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {
-    const int r = i / k, gr = row0 + r;
-    if (gr < n) {
-      idx_out[(int64_t)gr * k + (i % k)] = besti[i];
-      d2_out[(int64_t)gr * k + (i % k)] = bestd[i];
-    }
-  }
-}
-
-// idx_out [n, k] int32 (-1 where fewer than k other items exist), d2_out [n, k] squared Euclidean
-// distances, ascending per row.  sqn_work: n floats of scratch.
-extern "C" int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_out,
-                       float* d2_out, float* sqn_work, void* stream) {
-  if (n <= 0 || nf <= 0 || k <= 0 || k > KNN_MAXK || !data || !idx_out || !d2_out || !sqn_work) {
-    mde_set_error("mde_knn: invalid arguments (1 <= k <= %d)", KNN_MAXK);
-    return MDE_E_INVALID;
-  }
-  if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
-  hipStream_t st = mde_stream(stream);
-  hipLaunchKernelGGL(k_row_sqnorm, dim3(mde_grid(n * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, nf,
-                     data, sqn_work);
-  MDE_LAUNCH_CHECK();
-  const size_t lds = sizeof(float) * (size_t)(KNN_BM * KNN_KBP + KNN_BN * KNN_KBP + KNN_BM * (KNN_BN + 1)) +
-                     (size_t)KNN_BM * k * (sizeof(float) + sizeof(int));
-  static bool attr = false;
-  if (!attr) {
-    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr = true;
-  }
-  hipLaunchKernelGGL(k_knn, dim3((unsigned)((n + KNN_BM - 1) / KNN_BM)), dim3(MDE_BLOCK), lds, st, (int)n,
-                     nf, k, data, sqn_work, idx_out, d2_out);
-  MDE_LAUNCH_CHECK();
-  return MDE_OK;
-}
-
-// out[r] = |X[r]|^2 (f32, summed as k_knn's norms are): the row norms the approximate search takes.
+// out[r] = |X[r]|^2 (f32, summed as mde_knn's norms are): the row norms the approximate search takes.
 extern "C" int mde_row_sqnorm(int64_t n, int32_t nf, const float* data, float* out, void* stream) {
   if (n <= 0 || nf <= 0 || !data || !out) return MDE_E_INVALID;
   if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
@@ -287,13 +161,16 @@ extern "C" int mde_rows_subtract(int64_t n, int32_t nf, const float* data, const
   return MDE_OK;
 }
 
-// ---------------------------------------------------------------- query against corpus
-// The tile scheme of k_knn on two matrices and a 2-D grid: workgroup (x, y) owns query rows
+// ---------------------------------------------------------------- the search: self-join and query against corpus (DESIGN sections 6, 6f)
+// The Gram tile of mde_knn_tile.h on two matrices and a 2-D grid: workgroup (x, y) owns query rows
 // [64 x, 64 x + 64) and scans the corpus columns of slice y, [y * slice_cols, (y + 1) * slice_cols) cut at
 // n_c (slice_cols a multiple of 64; a slice past the end is empty and writes an empty list).  Its sorted
 // top-k goes to list y of the outputs, laid out [slices, n_q, k]: with one slice these are the final
-// outputs, otherwise scratch that k_knn_cross_merge folds.  Nothing is excluded as "self".  Columns are
-// offered in increasing index, so each list is ordered by (d2, index).
+// outputs, otherwise scratch that k_knn_cross_merge folds.  SELF: Q and C are one matrix (the exact
+// self-join of mde_knn) and a row does not list itself; otherwise nothing is excluded.  Columns are
+// offered in increasing index, so each list is ordered by (d2, index): insertion only when a candidate beats
+// the current k-th best, which becomes rare quickly.
+template <bool SELF>
 __global__ __launch_bounds__(MDE_BLOCK) void k_knn_cross(int n_q, int n_c, int nf, int k, int64_t slice_cols,
                                                          const float* __restrict__ Q, const float* __restrict__ C,
                                                          const float* __restrict__ qn,
@@ -301,82 +178,68 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_cross(int n_q, int n_c, int n
                                                          int32_t* __restrict__ idx_out,
                                                          float* __restrict__ d2_out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* sA = lds;                           // [KNN_BM][KNN_KBP]
-  float* sB = sA + KNN_BM * KNN_KBP;         // [KNN_BN][KNN_KBP]
-  float* sD = sB + KNN_BN * KNN_KBP;         // [KNN_BM][KNN_BN + 1] squared distances of the tile
-  float* bestd = sD + KNN_BM * (KNN_BN + 1); // [KNN_BM][k]
-  int* besti = reinterpret_cast<int*>(bestd + KNN_BM * k);  // [KNN_BM][k]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wj = wave & 1;   // quadrant of the 64x64 tile
+  const knn_tile_lds s = knn_tile_carve(lds, k, 0);
+  const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
   const int64_t lo = (int64_t)blockIdx.y * slice_cols;
   const int64_t c_lo = lo < n_c ? lo : n_c, c_hi = lo + slice_cols < n_c ? lo + slice_cols : n_c;
-  for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {
-    bestd[i] = 3.402823466e+38f;
-    besti[i] = -1;
-  }
+  knn_lists_init(s.bestd, s.besti, KNN_BM * k);
   float worst = 3.402823466e+38f;            // thread t < 64: current k-th best of row t
-  const int li = lane & 31, lk = lane >> 5;
+  // the rows this thread stages, (tid >> 5) + 8 q of either side: a row past the matrix reads its last row
+  // and is zeroed, so every load stays inside Q / C
+  const float* arow[KNN_STG];
+  bool aok[KNN_STG];
+#pragma unroll
+  for (int q = 0; q < KNN_STG; ++q) {
+    const int64_t gr = row0 + (tid >> 5) + 8 * q;
+    aok[q] = gr < n_q;
+    arow[q] = Q + (aok[q] ? gr : n_q - 1) * nf;
+  }
   for (int64_t col0 = c_lo; col0 < c_hi; col0 += KNN_BN) {
-    f32x16 acc;
+    const float* brow[KNN_STG];
+    bool bok[KNN_STG];
 #pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-    constexpr int STG = (KNN_BM * KNN_KB) / MDE_BLOCK;
-    float ra[STG], rb[STG];
-    auto fetch = [&](int k0) {
-#pragma unroll
-      for (int q = 0; q < STG; ++q) {
-        const int e = tid + q * MDE_BLOCK;
-        const int r = e >> 5, c = e & 31;
-        const int64_t gr = row0 + r, gc = col0 + r;
-        const int f = k0 + c;
-        // clamped addresses, zeroed afterwards (as in k_knn): every load stays inside Q / C
-        const int fc = f < nf ? f : nf - 1;
-        const float va = Q[(gr < n_q ? gr : n_q - 1) * nf + fc];
-        const float vb = C[(gc < n_c ? gc : n_c - 1) * nf + fc];
-        ra[q] = (gr < n_q && f < nf) ? va : 0.0f;
-        rb[q] = (gc < n_c && f < nf) ? vb : 0.0f;
-      }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < nf; k0 += KNN_KB) {
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < STG; ++q) {
-        const int e = tid + q * MDE_BLOCK;
-        const int r = e >> 5, c = e & 31;
-        sA[r * KNN_KBP + c] = ra[q];
-        sB[r * KNN_KBP + c] = rb[q];
-      }
-      __syncthreads();
-      if (k0 + KNN_KB < nf) fetch(k0 + KNN_KB);
-      const float* pa = sA + (wi * 32 + li) * KNN_KBP + lk;
-      const float* pb = sB + (wj * 32 + li) * KNN_KBP + lk;
-#pragma unroll
-      for (int kk = 0; kk < KNN_KB; kk += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[kk], pb[kk], acc, 0, 0, 0);
+    for (int q = 0; q < KNN_STG; ++q) {
+      const int64_t gc = col0 + (tid >> 5) + 8 * q;
+      bok[q] = gc < n_c;
+      brow[q] = C + (bok[q] ? gc : n_c - 1) * nf;
     }
-    // C/D map of the 32x32 tile: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int r = wi * 32 + (q & 3) + 8 * (q >> 2) + 4 * lk;
-      const int c = wj * 32 + li;
-      const int64_t gr = row0 + r, gc = col0 + c;
-      float d2 = 3.402823466e+38f;
-      if (gr < n_q && gc < n_c) d2 = fmaxf(qn[gr] + cn[gc] - 2.0f * acc[q], 0.0f);
-      sD[r * (KNN_BN + 1) + c] = d2;
-    }
+    const f32x16 acc = knn_gram_tile(s.sA, s.sB, nf, arow, aok, brow, bok);
+    knn_park_tile(
+        s.sD, acc,
+        [&](int r, int c) { return row0 + r < n_q && col0 + c < n_c && !(SELF && row0 + r == col0 + c); },
+        [&](int r) { return qn[row0 + r]; }, [&](int c) { return cn[col0 + c]; });
     __syncthreads();
     if (tid < KNN_BM)
-      mde_topk_merge(sD + tid * (KNN_BN + 1), KNN_BN, (int)col0, k, bestd + tid * k, besti + tid * k, worst);
+      mde_topk_merge(s.sD + tid * (KNN_BN + 1), KNN_BN, (int)col0, k, s.bestd + tid * k, s.besti + tid * k, worst);
   }
   __syncthreads();
   const int rows = n_q - row0 < KNN_BM ? (int)(n_q - row0) : KNN_BM;
   const int64_t base = ((int64_t)blockIdx.y * n_q + row0) * k;   // the block's rows are contiguous in list y
-  for (int i = tid; i < rows * k; i += MDE_BLOCK) {
-    idx_out[base + i] = besti[i];
-    d2_out[base + i] = bestd[i];
+  knn_lists_store(s.bestd, s.besti, rows * k, idx_out + base, d2_out + base);
+}
+
+// idx_out [n, k] int32 (-1 where fewer than k other items exist), d2_out [n, k] squared Euclidean
+// distances, ascending per row.  sqn_work: n floats of scratch.
+extern "C" int mde_knn(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_out,
+                       float* d2_out, float* sqn_work, void* stream) {
+  if (n <= 0 || nf <= 0 || k <= 0 || k > KNN_MAXK || !data || !idx_out || !d2_out || !sqn_work) {
+    mde_set_error("mde_knn: invalid arguments (1 <= k <= %d)", KNN_MAXK);
+    return MDE_E_INVALID;
   }
+  if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
+  hipStream_t st = mde_stream(stream);
+  hipLaunchKernelGGL(k_row_sqnorm, dim3(mde_grid(n * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, nf,
+                     data, sqn_work);
+  MDE_LAUNCH_CHECK();
+  const int rc = knn_raise_lds_limit<k_knn_cross<true>>(96 * 1024);
+  if (rc != MDE_OK) return rc;
+  // one slice of every column tile: the self-join does not split the corpus
+  hipLaunchKernelGGL(k_knn_cross<true>, dim3((unsigned)((n + KNN_BM - 1) / KNN_BM)), dim3(MDE_BLOCK),
+                     knn_tile_lds_bytes(k, 0), st, (int)n, (int)n, nf, k, (n + KNN_BN - 1) / KNN_BN * KNN_BN, data, data,
+                     sqn_work, sqn_work, idx_out, d2_out);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
 }
 
 // Folds the `slices` sorted lists of every query row ([slices, n_q, k], empty slots FLT_MAX / -1) into the
@@ -395,10 +258,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_cross_merge(int n_q, int k, i
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
   const int rows = n_q - row0 < KNN_BM ? (int)(n_q - row0) : KNN_BM;
-  for (int i = tid; i < KNN_BM * k; i += MDE_BLOCK) {
-    bestd[i] = 3.402823466e+38f;
-    besti[i] = -1;
-  }
+  knn_lists_init(bestd, besti, KNN_BM * k);
   float worst_d = 3.402823466e+38f;
   int worst_i = -1;
   for (int s = 0; s < slices; ++s) {
@@ -413,10 +273,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_cross_merge(int n_q, int k, i
       mde_topk_merge_id(sd + tid * k, si + tid * k, k, k, bestd + tid * k, besti + tid * k, worst_d, worst_i);
   }
   __syncthreads();
-  for (int i = tid; i < rows * k; i += MDE_BLOCK) {
-    idx_out[row0 * k + i] = besti[i];
-    d2_out[row0 * k + i] = bestd[i];
-  }
+  knn_lists_store(bestd, besti, rows * k, idx_out + row0 * k, d2_out + row0 * k);
 }
 
 // The automatic slice count (slices == 0).  Rule: when the query blocks alone give every CU a workgroup
@@ -496,22 +353,15 @@ extern "C" int mde_knn_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* 
   hipLaunchKernelGGL(k_row_sqnorm, dim3(mde_grid(n_c * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_c, nf, C,
                      cn);
   MDE_LAUNCH_CHECK();
-  const size_t lds = sizeof(float) * (size_t)(KNN_BM * KNN_KBP + KNN_BN * KNN_KBP + KNN_BM * (KNN_BN + 1)) +
-                     (size_t)KNN_BM * k * (sizeof(float) + sizeof(int));
   const size_t lds_merge = (size_t)KNN_BM * k * 2 * (sizeof(float) + sizeof(int));
-  static bool attr = false;
-  if (!attr) {
-    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_cross),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_cross_merge),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr = true;
-  }
+  int rc = knn_raise_lds_limit<k_knn_cross<false>>(96 * 1024);
+  if (rc == MDE_OK) rc = knn_raise_lds_limit<k_knn_cross_merge>(96 * 1024);
+  if (rc != MDE_OK) return rc;
   const int64_t tiles = (n_c + KNN_BN - 1) / KNN_BN;
   const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;    // whole tiles; the last slices may be short or empty
   const unsigned qb = (unsigned)((n_q + KNN_BM - 1) / KNN_BM);
-  hipLaunchKernelGGL(k_knn_cross, dim3(qb, (unsigned)s), dim3(MDE_BLOCK), lds, st, (int)n_q, (int)n_c, nf, k,
-                     slice_cols, Q, C, qn, cn, s > 1 ? pi : idx_out, s > 1 ? pd : d2_out);
+  hipLaunchKernelGGL(k_knn_cross<false>, dim3(qb, (unsigned)s), dim3(MDE_BLOCK), knn_tile_lds_bytes(k, 0), st,
+                     (int)n_q, (int)n_c, nf, k, slice_cols, Q, C, qn, cn, s > 1 ? pi : idx_out, s > 1 ? pd : d2_out);
   MDE_LAUNCH_CHECK();
   if (s > 1) {
     hipLaunchKernelGGL(k_knn_cross_merge, dim3(qb), dim3(MDE_BLOCK), lds_merge, st, (int)n_q, k, (int)s, pd, pi,

@@ -3,8 +3,7 @@
 // and the per-edge distance kernel of every metric.  Definitions follow scipy.spatial.distance
 // (cosine 1 - u.v / (|u| |v|), correlation = cosine of the row-centred vectors, cityblock sum |u - v|);
 // the reference has no metric keyword (its pynndescent call is Euclidean).
-#include "mde_common.h"
-#include "mde_topk.h"
+#include "mde_knn_tile.h"
 
 // ------------------------------------------------------------------ unit rows for cosine / correlation
 // One wave per row (as k_row_sqnorm): the sum (for the mean), the squared norm of the centred row (both in
@@ -74,7 +73,7 @@ extern "C" int mde_rows_normalize(int64_t n, int32_t nf, const float* data, int3
 }
 
 // ------------------------------------------------------------------ exact Manhattan k-NN
-// The workgroup shape of k_knn (mde_knn.hip): 256 threads own 64 query rows and walk the candidates 64 at
+// The workgroup shape of the Euclidean tile (mde_knn_tile.h): 256 threads own 64 query rows and walk the candidates 64 at
 // a time; there is no matrix-core form of sum |x - y|, so each thread holds a 4 x 4 register tile of the
 // 64 x 64 block of partial sums (thread (ty, tx) = (tid >> 4, tid & 15): rows 4 ty .., candidates 4 tx ..).
 // Feature chunks of 32 are staged through LDS FEATURE-major, [feature][row], so that the four rows (or
@@ -90,7 +89,6 @@ extern "C" int mde_rows_normalize(int64_t n, int32_t nf, const float* data, int3
 #define L1_BN 64
 #define L1_KB 32
 #define L1_LD 68
-#define L1_MAXK 64
 
 // acc += |d| as ONE v_add_f32 with the absolute value as a source modifier.  Written as acc += fabsf(d) the
 // compiler pairs the accumulators into v_pk_add_f32, which has no abs modifier, and spends a v_and_b32 per
@@ -112,10 +110,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_l1(int n, int nf, int k, cons
   const int tx = tid & 15, ty = tid >> 4;
   const int sc = tid & 31, sg = tid >> 5;
   const int row0 = blockIdx.x * L1_BM;
-  for (int i = tid; i < L1_BM * k; i += MDE_BLOCK) {
-    bestd[i] = 3.402823466e+38f;
-    besti[i] = -1;
-  }
+  knn_lists_init(bestd, besti, L1_BM * k);
   float worst = 3.402823466e+38f;            // thread t < 64: current k-th best of row t
   for (int col0 = 0; col0 < n; col0 += L1_BN) {
     float acc[4][4];
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_l1(int n, int nf, int k, cons
         for (int i = 0; i < 4; ++i) {
           const int r = (sg + 8 * q) * 4 + i;
           const int gr = row0 + r, gc = col0 + r;
-          // plain loads from clamped addresses, zeroed afterwards (as k_knn: no branch around a load)
+          // plain loads from clamped addresses, zeroed afterwards (as knn_gram_tile: no branch around a load)
           const float va = X[(int64_t)(gr < n ? gr : n - 1) * nf + fc];
           const float vb = X[(int64_t)(gc < n ? gc : n - 1) * nf + fc];
           ra[q][i] = (gr < n && f < nf) ? va : 0.0f;
@@ -178,6 +173,8 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_l1(int n, int nf, int k, cons
       mde_topk_merge(sD + tid * (L1_BN + 1), L1_BN, col0, k, bestd + tid * k, besti + tid * k, worst);
   }
   __syncthreads();
+  // its own write-out, not knn_lists_store: with the helper the kernel measured 0.8 % slower at 70k x 784
+  // (profiles/r11_knn_tile.txt) although the arithmetic loop compiled to the same instructions
   for (int i = tid; i < L1_BM * k; i += MDE_BLOCK) {
     const int r = i / k, gr = row0 + r;
     if (gr < n) {
@@ -191,19 +188,15 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_l1(int n, int nf, int k, cons
 // distance itself, not a square), ascending per row, ties to the smaller index.
 extern "C" int mde_knn_l1(int64_t n, int32_t nf, const float* data, int32_t k, int32_t* idx_out, float* d_out,
                           void* stream) {
-  if (n <= 0 || nf <= 0 || k <= 0 || k > L1_MAXK || !data || !idx_out || !d_out) {
-    mde_set_error("mde_knn_l1: invalid arguments (1 <= k <= %d)", L1_MAXK);
+  if (n <= 0 || nf <= 0 || k <= 0 || k > KNN_MAXK || !data || !idx_out || !d_out) {
+    mde_set_error("mde_knn_l1: invalid arguments (1 <= k <= %d)", KNN_MAXK);
     return MDE_E_INVALID;
   }
   if (n >= ((int64_t)1 << 31)) return MDE_E_TOO_LARGE;
   const size_t lds = sizeof(float) * (size_t)(2 * L1_KB * L1_LD + L1_BM * (L1_BN + 1)) +
                      (size_t)L1_BM * k * (sizeof(float) + sizeof(int));
-  static bool attr = false;
-  if (!attr) {
-    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_l1),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr = true;
-  }
+  const int rc = knn_raise_lds_limit<k_knn_l1>(96 * 1024);
+  if (rc != MDE_OK) return rc;
   hipLaunchKernelGGL(k_knn_l1, dim3((unsigned)((n + L1_BM - 1) / L1_BM)), dim3(MDE_BLOCK), lds, mde_stream(stream),
                      (int)n, nf, k, data, idx_out, d_out);
   MDE_LAUNCH_CHECK();

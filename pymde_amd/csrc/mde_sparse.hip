@@ -25,15 +25,13 @@
 #include <float.h>
 #include <limits.h>
 
-#include "mde_common.h"
-#include "mde_topk.h"
+#include "mde_knn_tile.h"   // KNN_MAXK, knn_raise_lds_limit: the panel kernel below has its own tile
 
 #define SPK_Q 128       // query rows per workgroup (two per lane)
 #define SPK_C 128       // candidates per tile
 #define SPK_CW 32       // candidates per wave
 #define SPK_G 8         // candidates whose first 64 entries are loaded together
 #define SPK_DS 65       // row stride of the parked d2 half-tile [SPK_Q][64 + 1]
-#define SPK_MAXK 64
 #define SPK_MIN_W 72    // the parked half-tile (SPK_Q x SPK_DS floats) must fit in the panel
 
 // 64-bit wave-uniform value of lane l
@@ -299,8 +297,8 @@ static int spk_window(int k, int nf, size_t* lds_bytes) {
 extern "C" int mde_sparse_knn(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
                               const float* values, int32_t k, int32_t* idx_out, float* d2_out, float* sqn_work,
                               void* stream) {
-  if (k <= 0 || k > SPK_MAXK || !idx_out || !d2_out || !sqn_work) {
-    mde_set_error("mde_sparse_knn: invalid arguments (1 <= k <= %d)", SPK_MAXK);
+  if (k <= 0 || k > KNN_MAXK || !idx_out || !d2_out || !sqn_work) {
+    mde_set_error("mde_sparse_knn: invalid arguments (1 <= k <= %d)", KNN_MAXK);
     return MDE_E_INVALID;
   }
   hipStream_t st = mde_stream(stream);
@@ -311,12 +309,8 @@ extern "C" int mde_sparse_knn(int64_t n, int32_t nf, int64_t nnz, const int64_t*
   MDE_LAUNCH_CHECK();
   size_t lds = 0;
   const int W = spk_window(k, nf, &lds);
-  static bool attr = false;
-  if (!attr) {
-    MDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sparse_knn),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  const int rc_lds = knn_raise_lds_limit<k_sparse_knn>(160 * 1024);
+  if (rc_lds != MDE_OK) return rc_lds;
   hipLaunchKernelGGL(k_sparse_knn, dim3((unsigned)((n + SPK_Q - 1) / SPK_Q)), dim3(MDE_BLOCK), lds, st, (int)n,
                      (int)nf, (int)k, W, indptr, indices, values, sqn_work, idx_out, d2_out);
   MDE_LAUNCH_CHECK();

@@ -1,5 +1,6 @@
-// mde_topk.h -- the per-row top-k merge shared by the dense (mde_knn.hip) and sparse (mde_sparse.hip)
-// exact k-NN kernels.
+// mde_topk.h -- the per-row top-k merges of the five k-NN kernels: by arrival order (mde_topk_merge) in
+// k_knn_cross (mde_knn.hip), k_knn_l1 (mde_metric.hip) and k_sparse_knn (mde_sparse.hip), by (d2, index)
+// (mde_topk_merge_id) in k_ann_scan (mde_ann.hip) and k_knn_cross_merge (mde_knn.hip).
 #pragma once
 #include "mde_common.h"
 

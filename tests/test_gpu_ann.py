@@ -78,7 +78,7 @@ def test_full_probe_equals_exact(nf):
         np.testing.assert_array_equal(wa, w)
         idx, d2 = preprocess._dense_knn_lists(X, k)
         idx_a, d2_a = _ann_lists(X, k, n_probe=10 ** 6)
-        torch.testing.assert_close(d2_a, d2, rtol=1e-6, atol=0)
+        assert torch.equal(d2_a, d2)
         assert torch.equal(idx_a, idx)
 
 
