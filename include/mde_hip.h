@@ -295,6 +295,25 @@ int mde_rows_subtract(int64_t n, int32_t nf, const float* data, const double* mu
 int64_t mde_knn_cross_work_bytes(int64_t n_q, int64_t n_c, int32_t k, int32_t slices);
 int mde_knn_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t k,
                   int32_t slices, int32_t* idx_out, float* d2_out, void* work, void* stream);
+/* The two-stage Euclidean search (csrc/mde_knn_bf16.hip): every pair of a row of Q [n_q, nf]
+ * and a row of C [n_c, nf] (float32, row-major, on the device) is ranked by a bf16 Gram product on the bf16
+ * matrix cores, every query keeps a shortlist of its n_cand best by (bf16 d2, index), and the shortlist is
+ * re-ranked with the float32 squared distance of mde_knn / mde_knn_cross: a returned pair's d2 has the bits
+ * those kernels give it, and when the true k nearest are all on the shortlist the result is theirs.
+ * The bf16 copies are of the rows minus mu (double [nf] on the device, one vector for Q and C, subtracted in
+ * double; NULL: the rows as given) and serve the shortlist only; the re-rank reads Q and C themselves.
+ * self != 0: Q == C and n_q == n_c (the self-join), and a row does not list itself.
+ * Outputs as for mde_knn_cross: idx_out [n_q, k] int32 (-1 in the slots beyond the rows available), d2_out
+ * [n_q, k], each row ordered by (d2, index).  1 <= k <= n_cand <= 64; n_q, n_c < 2^31.
+ * slices: the corpus split of the shortlist kernel, as in mde_knn_cross but in 128-row query blocks and
+ * 128-column tiles (0: automatic); the shortlist, and so the result, is identical for every split.
+ * work: mde_knn_bf16_work_bytes(...) bytes of scratch (the bf16 copies at a row stride of nf rounded up to
+ * 32, four vectors of norms, the shortlist and the per-slice lists); the call allocates nothing.  Arguments are
+ * checked on the host before any launch: MDE_E_INVALID with a message.  ASYNC. */
+int64_t mde_knn_bf16_work_bytes(int64_t n_q, int64_t n_c, int32_t nf, int32_t k, int32_t n_cand, int32_t slices);
+int mde_knn_bf16(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, const double* mu,
+                 int32_t self, int32_t k, int32_t n_cand, int32_t slices, int32_t* idx_out, float* d2_out,
+                 void* work, void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

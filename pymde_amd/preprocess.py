@@ -22,6 +22,63 @@ from pymde_amd import util
 
 _LOGGER = logging.getLogger("__pymde_amd__")   # problem.LOGGER
 
+FLOAT32, BFLOAT16 = "float32", "bfloat16"
+PRECISIONS = {"float32": FLOAT32, "fp32": FLOAT32, "f32": FLOAT32, "bfloat16": BFLOAT16, "bf16": BFLOAT16}
+MAX_CANDIDATES = 64      # KNN_MAXK of csrc/mde_knn_tile.h: the longest shortlist
+
+
+def resolve_precision(precision):
+    """``"float32"`` or ``"bfloat16"`` for a ``precision=`` value or alias (case-insensitive); ``ValueError``
+    for anything else.  Needs no device."""
+    name = precision.strip().lower() if isinstance(precision, str) else precision
+    if not isinstance(name, str) or name not in PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; the neighbour searches run in 'float32' (the default) "
+                         "or 'bfloat16' (alias 'bf16': a bfloat16 shortlist re-ranked in float32)")
+    return PRECISIONS[name]
+
+
+def default_n_candidates(k, available=None):
+    """The shortlist length of the bfloat16 search for ``k`` neighbours: ``min(64, max(2 k, k + 16))``, and no
+    longer than the ``available`` corpus rows (but never shorter than ``k``)."""
+    k = int(k)
+    n_cand = min(MAX_CANDIDATES, max(2 * k, k + 16))
+    if available is not None:
+        n_cand = min(n_cand, max(int(available), k))
+    return max(n_cand, k)
+
+
+def _check_precision_arguments(precision, n_candidates, k, metric, approximate=False, graph=False):
+    """The argument errors of the bfloat16 search that need no device; returns the canonical precision."""
+    precision = resolve_precision(precision)
+    if precision != BFLOAT16:
+        if n_candidates is not None:
+            raise ValueError("n_candidates is the shortlist length of precision='bfloat16'; the float32 search has "
+                             "no shortlist")
+        return precision
+    if metric == _metrics.MANHATTAN:
+        raise ValueError("precision='bfloat16' has no Manhattan search (the shortlist is a Gram product); the "
+                         "metrics it serves are 'euclidean', 'cosine' and 'correlation'")
+    if graph:
+        raise ValueError("precision='bfloat16' applies to data matrices; a Graph has its own shortest-path search")
+    if approximate:
+        raise ValueError("precision='bfloat16' with approximate=True is not served: the inverted-file scan is "
+                         "float32; use one or the other")
+    if n_candidates is not None:
+        n_candidates, k = int(n_candidates), int(k)
+        if n_candidates < k or n_candidates > MAX_CANDIDATES:
+            raise ValueError(f"n_candidates must lie in [k, {MAX_CANDIDATES}] (k = {k}, got {n_candidates})")
+    return precision
+
+
+def _resolve_n_candidates(n_candidates, k, available):
+    """The shortlist length for ``k`` (already clamped to the rows available) neighbours."""
+    if n_candidates is None:
+        return default_n_candidates(k, available)
+    n_candidates = int(n_candidates)
+    if n_candidates < k or n_candidates > MAX_CANDIDATES:
+        raise ValueError(f"n_candidates must lie in [k, {MAX_CANDIDATES}] (k = {k}, got {n_candidates})")
+    return n_candidates
+
 
 def _edges_on_device(edges, device=None):
     if not isinstance(edges, torch.Tensor):
@@ -104,7 +161,8 @@ def _neighbor_lists_to_graph(n, k, idx, values, max_value, device):
 
 
 def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,
-                        n_lists=None, n_probe=None, seed=0, verbose=False, metric="euclidean"):
+                        n_lists=None, n_probe=None, seed=0, verbose=False, metric="euclidean",
+                        precision="float32", n_candidates=None):
     """Exact k-nearest-neighbour graph of the rows of a data matrix (Euclidean distance by default)
     [ref: preprocess/data_matrix.py:91-178] or of the nodes of a ``Graph`` (shortest-path metric,
     ``pymde_amd.graph.k_nearest_neighbors``) [ref: preprocess/generic.py dispatch].
@@ -149,9 +207,26 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     cosine (its rows are scaled in place of a copy) and is densified under correlation and Manhattan (an
     error if the dense copy does not fit).  Manhattan has an exact kernel of its own and no approximate
     search.  A row without a direction (all zero under cosine, constant under correlation) is an error.
-    See ``pymde_amd.metrics``."""
+    See ``pymde_amd.metrics``.
+
+    ``precision="bfloat16"`` (alias ``"bf16"``; data matrices, not Manhattan, not ``approximate=True``)
+    selects the two-stage search (``mde_knn_bf16``): every pair is ranked by a bfloat16
+    Gram product on the bfloat16 matrix cores, each row keeps a shortlist of ``n_candidates`` rows, and the
+    shortlist is re-ranked with the float32 squared distances of the float32 search, bit for bit.  The result
+    is the float32 result whenever the bfloat16 ranking keeps each row's true ``k`` nearest within its
+    shortlist; a neighbour it misses is replaced by the next nearest one, and every returned distance is
+    still the float32 distance of its pair.  ``n_candidates`` defaults to ``min(64, max(2 k, k + 16))`` (at
+    most the other rows there are) and must lie in ``[k, 64]``: above k = 48 the margin shrinks below 16 and
+    at k = 64 there is none, so recall falls below 1 there.  The bfloat16 copy is always of the rows minus
+    their column means (on the grid of ``metrics.grid_means``): bfloat16 keeps 8 significant bits and an
+    offset would use them up.  It takes ``2 n n_features`` bytes (rows padded to a multiple of 32) beside what
+    the float32 search takes.  Data whose neighbours differ by less than bfloat16 resolves -- points on a
+    line, say -- lose recall.  A sparse matrix is served when it is densified; one that would stay on the
+    sparse kernel is an error.  ``verbose=True`` logs a recall@k estimated on 1 000 sampled rows against the
+    float32 search."""
     metric = _metrics.resolve(metric)
     _metrics.check_approximate(metric, approximate)
+    precision = _check_precision_arguments(precision, n_candidates, k, metric, approximate, _is_graph(data))
     if hasattr(data, "edges") and hasattr(data, "n_items") and not isinstance(data, torch.Tensor):
         _metrics.check_graph(metric)
         if approximate:
@@ -161,7 +236,7 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
                                           max_distance=max_distance)
     if metric != _metrics.EUCLIDEAN:
         idx, values, bound = _metric_knn_lists(data, k, metric, max_distance, device, approximate, n_lists,
-                                               n_probe, seed, verbose)
+                                               n_probe, seed, verbose, precision, n_candidates)
         return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
     if _sparse.is_sparse(data):
         csr = _sparse.to_device_csr(data, device)
@@ -176,7 +251,10 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
                     "use approximate=False (the exact sparse kernel)")
             idx, d2 = _euclidean_knn_lists(csr.to_dense(), k, True, n_lists, n_probe, seed, verbose)
         elif _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
-            idx, d2 = _euclidean_knn_lists(csr.to_dense(), k)
+            idx, d2 = _euclidean_knn_lists(csr.to_dense(), k, verbose=verbose, precision=precision,
+                                           n_candidates=n_candidates)
+        elif precision == BFLOAT16:
+            raise ValueError(_BF16_SPARSE_DOES_NOT_FIT.format(n=csr.n, nf=csr.n_features))
         else:
             _check_finite_csr(csr)
             idx, d2 = _sparse_knn_lists(csr, k)
@@ -192,13 +270,18 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     k = _clamp_k(k, n)
     if approximate:
         _ann.resolve_params(n, n_lists, n_probe)      # the same argument checks at every size
-    idx, d2 = _euclidean_knn_lists(data, k, approximate, n_lists, n_probe, seed, verbose)
+    idx, d2 = _euclidean_knn_lists(data, k, approximate, n_lists, n_probe, seed, verbose, precision, n_candidates)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
     return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
 
 
+_BF16_SPARSE_DOES_NOT_FIT = (
+    "precision='bfloat16' densifies sparse data, and the dense copy of this {n} x {nf} matrix does not fit in "
+    "the device memory allowed for it; use precision='float32' (the exact sparse kernel)")
+
+
 def _metric_knn_lists(data, k, metric, max_distance=None, device=None, approximate=False, n_lists=None,
-                      n_probe=None, seed=0, verbose=False):
+                      n_probe=None, seed=0, verbose=False, precision=FLOAT32, n_candidates=None):
     """Directed neighbour lists of a data matrix under cosine, correlation or Manhattan (a canonical name):
     ``(idx [n, k] int32, values [n, k], bound)``.  ``values`` are what the kernels rank by -- the squared
     chord ``d2 = 2 (1 - cos)`` of the unit rows for cosine / correlation, the distance itself for Manhattan
@@ -238,9 +321,14 @@ def _metric_knn_lists(data, k, metric, max_distance=None, device=None, approxima
     if metric == _metrics.MANHATTAN:
         idx, values = _metrics.manhattan_knn_lists(data, k)
     elif csr is not None:
+        if precision == BFLOAT16:
+            raise ValueError(_BF16_SPARSE_DOES_NOT_FIT.format(n=csr.n, nf=csr.n_features))
         idx, values = _sparse_knn_lists(csr, k)
     elif approximate and n >= _ann.MIN_ITEMS:
         idx, values = _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
+    elif precision == BFLOAT16:
+        # the unit rows are searched as they are by the float32 kernel; the bfloat16 copy is centred
+        idx, values = _bf16_self_search(data, k, n_candidates, _bf16_mu(data), verbose, seed)
     else:
         idx, values = _dense_knn_lists(data, k)
     if max_distance is None:
@@ -257,13 +345,18 @@ def _clamp_k(k, n):
     return k
 
 
-def _euclidean_knn_lists(data, k, approximate=False, n_lists=None, n_probe=None, seed=0, verbose=False):
+def _euclidean_knn_lists(data, k, approximate=False, n_lists=None, n_probe=None, seed=0, verbose=False,
+                         precision=FLOAT32, n_candidates=None):
     """Directed Euclidean neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the GPU:
     what ``k_nearest_neighbors`` calls for Euclidean data.  The search -- exact, or the inverted file with its
     recall estimate when ``approximate`` and n >= ``ann.MIN_ITEMS`` -- runs on the rows minus their float64
     column means when the offset of the data dominates its spread (``metrics.translated_rows``, DESIGN
     section 6), on ``data`` itself otherwise.  ``ValueError`` for a row that holds NaN or infinity, before
-    any list is produced."""
+    any list is produced.  ``precision=BFLOAT16``: the two-stage search on the same float32 rows, its bfloat16
+    copy centred whether or not the float32 rows are (``_bf16_rows``)."""
+    if precision == BFLOAT16:
+        rows, mu, _ = _bf16_rows(data)
+        return _bf16_self_search(rows, k, n_candidates, mu, verbose, seed)
     data, _ = _metrics.translated_rows(data)
     if approximate and int(data.shape[0]) >= _ann.MIN_ITEMS:
         return _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
@@ -291,6 +384,72 @@ def _dense_knn_lists(data, k):
     with torch.cuda.device(device):
         _lib.check(lib.mde_knn(n, nf, _lib.ptr(data), k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(sqn),
                                _lib.stream_ptr(device)))
+    return idx, d2
+
+
+def _bf16_mu(data, what="the data matrix"):
+    """The float64 [nf] vector on the device by which the bfloat16 copy of a search of the corpus ``data``
+    (dense float32 on the GPU) is centred: its column means on the grid of ``metrics.grid_means``."""
+    mean, var = _metrics.column_stats(data, what)
+    return _metrics.grid_means(mean, var).to(data.device)
+
+
+def _bf16_rows(data, what="the data matrix"):
+    """What the bfloat16 search of the corpus ``data`` (dense float32 on the GPU) runs on: ``(rows, mu,
+    shift)``.  ``rows`` are the float32 rows of the float32 search -- ``data`` minus ``shift``, the grid column
+    means, when ``metrics.translation_pays``, ``data`` itself (``shift`` None) otherwise -- and ``mu`` is what
+    remains to be subtracted for the bfloat16 copy: None for rows that are centred already, the grid column
+    means otherwise.  ``ValueError`` for a row that holds NaN or infinity."""
+    mean, var = _metrics.column_stats(data, what)
+    mu = _metrics.grid_means(mean, var).to(data.device)
+    if _metrics.translation_pays(mean, var):
+        return _metrics.subtract_columns(data, mu), None, mu
+    return data, mu, None
+
+
+def _knn_bf16(queries, data, self_join, k, n_candidates, mu, slices):
+    n_q, n_c, nf = int(queries.shape[0]), int(data.shape[0]), int(data.shape[1])
+    device = data.device
+    lib = _lib.load()
+    idx = torch.empty((n_q, k), dtype=torch.int32, device=device)
+    d2 = torch.empty((n_q, k), dtype=torch.float32, device=device)
+    if mu is not None:
+        mu = mu.to(device=device, dtype=torch.float64).contiguous()
+    with torch.cuda.device(device):
+        nbytes = int(lib.mde_knn_bf16_work_bytes(n_q, n_c, nf, k, n_candidates, slices))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.mde_knn_bf16(n_q, n_c, nf, _lib.ptr(queries), _lib.ptr(data), _lib.ptr(mu), int(self_join), k,
+                                    n_candidates, slices, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(work),
+                                    _lib.stream_ptr(device)))
+    return idx, d2
+
+
+def _dense_knn_lists_bf16(data, k, n_candidates=None, mu=None, slices=0):
+    """``_dense_knn_lists`` by the two-stage search ``mde_knn_bf16``: the bfloat16 shortlist of ``n_candidates``
+    per row (default ``default_n_candidates``) of the rows minus ``mu`` (float64 [nf]; None: the rows as
+    given), re-ranked with the float32 distances of ``mde_knn`` on ``data`` itself."""
+    k = int(k)
+    n_candidates = _resolve_n_candidates(n_candidates, k, int(data.shape[0]) - 1)
+    return _knn_bf16(data, data, True, k, n_candidates, mu, slices)
+
+
+def _cross_knn_lists_bf16(queries, data, k, n_candidates=None, mu=None, slices=0):
+    """``_cross_knn_lists`` by the two-stage search ``mde_knn_bf16``; ``mu`` centres the bfloat16 copies of
+    both matrices."""
+    k = int(k)
+    n_candidates = _resolve_n_candidates(n_candidates, k, int(data.shape[0]))
+    return _knn_bf16(queries, data, False, k, n_candidates, mu, slices)
+
+
+def _bf16_self_search(rows, k, n_candidates, mu, verbose=False, seed=0):
+    idx, d2 = _dense_knn_lists_bf16(rows, k, n_candidates, mu)
+    if verbose:
+        n_cand = _resolve_n_candidates(n_candidates, k, int(rows.shape[0]) - 1)
+        recall = _estimated_recall(rows, idx, k, seed=seed)
+        _LOGGER.info(f"bfloat16 {k}-NN: shortlist of {n_cand} per row, estimated recall@{k} {recall:.4f} against "
+                     "the float32 search (1000 sampled rows)")
     return idx, d2
 
 
@@ -346,7 +505,8 @@ def _cross_knn_lists(queries, data, k, slices=0):
     return idx, d2
 
 
-def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclidean", device=None):
+def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclidean", device=None,
+                            precision="float32", n_candidates=None):
     """For every row of ``queries`` [n_q, n_features] its ``k`` nearest rows of ``data`` [n_c, n_features]:
     the exact query-against-corpus search (``mde_knn_cross``).  The reference leaves
     this search to the user; here it is what ``recipes.extend_embedding`` places new points with.
@@ -365,8 +525,15 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
     matrix is an error.  The Euclidean search runs on both matrices minus the column means of ``data`` when
     that offset dominates the spread of ``data`` (as in ``k_nearest_neighbors``), and a row of either matrix
     that holds NaN or infinity is a ``ValueError`` naming the argument and the row.  There is no Manhattan cross kernel and no approximate cross search; a ``Graph``
-    is not a data matrix."""
+    is not a data matrix.
+
+    ``precision="bfloat16"`` and ``n_candidates`` as in ``k_nearest_neighbors``: a bfloat16 shortlist of
+    ``n_candidates`` rows of ``data`` per query (default ``min(64, max(2 k, k + 16))``, at most the rows of
+    ``data``), re-ranked with the float32 distances of the float32 search; the bfloat16 copies of both
+    matrices are centred at the column means of ``data``."""
     metric = _metrics.resolve(metric)
+    precision = _check_precision_arguments(precision, n_candidates, k, metric,
+                                           graph=_is_graph(queries) or _is_graph(data))
     if metric == _metrics.MANHATTAN:
         raise ValueError("cross_nearest_neighbors has no Manhattan kernel; the metrics it serves are "
                          "'euclidean', 'cosine' and 'correlation'")
@@ -390,16 +557,28 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
     device = util.require_cuda_device(device)
     Q = _dense_rows_for_cross(queries, device, "queries")
     C = _dense_rows_for_cross(data, device, "data")
+    mu = None
     if metric != _metrics.EUCLIDEAN:
         if n_q:
             Q = _metrics.normalized_rows(Q, metric)
         C = _metrics.normalized_rows(C, metric)
+        if precision == BFLOAT16:
+            mu = _bf16_mu(C, "`data`")
+    elif precision == BFLOAT16:
+        if n_q:
+            _metrics.check_finite(Q, "`queries`")
+        C, mu, shift = _bf16_rows(C, "`data`")
+        if shift is not None and n_q:
+            Q = _metrics.subtract_columns(Q, shift)
     else:
         Q, C = _translated_pair(Q, C)
     if n_q == 0:
         return (torch.empty((0, k), dtype=torch.int64, device=device),
                 torch.empty((0, k), dtype=torch.float32, device=device))
-    idx32, d2 = _cross_knn_lists(Q, C, k)
+    if precision == BFLOAT16:
+        idx32, d2 = _cross_knn_lists_bf16(Q, C, k, n_candidates, mu)
+    else:
+        idx32, d2 = _cross_knn_lists(Q, C, k)
     dist = d2.sqrt() if metric == _metrics.EUCLIDEAN else 0.5 * d2
     empty = idx32 < 0
     if max_distance is not None:

@@ -175,7 +175,8 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
 def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p,
                        repulsive_penalty=penalties.Log, constraint=None, n_neighbors=None,
                        repulsive_fraction=None, max_distance=None, init="quadratic", device=None,
-                       verbose=False, seed=None, approximate_neighbors=False, metric="euclidean"):
+                       verbose=False, seed=None, approximate_neighbors=False, metric="euclidean",
+                       neighbor_precision="float32"):
     """An MDE problem that preserves the k-nearest-neighbour structure of a data matrix
     (rows = items) [ref: recipes.py:221-448]: k-NN graph (weights 1 / 2), optional spectral
     initialisation, uniformly sampled repulsive edges (weight -1), ``PushAndPull`` of the two
@@ -191,9 +192,15 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
 
     ``metric`` (data matrices only): the distance in the original data under which neighbours are taken,
     as for ``preprocess.k_nearest_neighbors`` -- ``"euclidean"``, ``"cosine"``, ``"correlation"`` or
-    ``"manhattan"``; ``max_distance`` is in its units.  The embedding side does not change."""
+    ``"manhattan"``; ``max_distance`` is in its units.  The embedding side does not change.
+
+    ``neighbor_precision`` (data matrices only): ``"bfloat16"`` builds the k-NN graph by the bfloat16
+    shortlist with float32 re-ranking of ``preprocess.k_nearest_neighbors(precision="bfloat16")``; not with
+    Manhattan or ``approximate_neighbors``."""
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
+    neighbor_precision = preprocess._check_precision_arguments(
+        neighbor_precision, None, 1, metric, approximate_neighbors not in (None, False), is_graph)
     if is_graph:
         _metrics.check_graph(metric)
     knn_options = _approximate_options(approximate_neighbors)
@@ -236,6 +243,9 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
             knn_options["verbose"] = verbose
         if metric != _metrics.EUCLIDEAN:
             knn_options["metric"] = metric
+        if neighbor_precision != preprocess.FLOAT32:
+            knn_options["precision"] = neighbor_precision
+            knn_options["verbose"] = verbose
         edges, weights = preprocess.k_nearest_neighbors(data, k=n_neighbors, max_distance=max_distance,
                                                         device=device, **knn_options)
     if isinstance(constraint, constraints.Anchored):
@@ -309,7 +319,7 @@ def _sample_new_item_edges(n_old, n_new, count, exclude, generator, device):
 
 def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repulsive_penalty=penalties.Log,
                      n_neighbors=None, repulsive_fraction=None, max_distance=None, metric="euclidean",
-                     device=None, verbose=False, seed=None):
+                     device=None, verbose=False, seed=None, neighbor_precision="float32"):
     """An MDE problem that places new points into an existing embedding: ``data`` [n_old, n_features] are
     the rows already embedded, ``X`` [n_old, m] their embedding (the embedding dimension is taken from it;
     it is used as float32), ``new_data`` [n_new, n_features] the rows to add.  The reference documents
@@ -333,8 +343,12 @@ def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repu
 
     The solve starts from ``X`` for the old rows and, for each new row, from the mean of its neighbours'
     rows of ``X`` (perturbed by 1e-4 when that leaves an edge of length zero).  An embedding that was
-    ``Standardized`` does not stay standardized once new rows are added."""
+    ``Standardized`` does not stay standardized once new rows are added.
+
+    ``neighbor_precision="bfloat16"`` takes the neighbours by
+    ``preprocess.cross_nearest_neighbors(precision="bfloat16")``."""
     metric = _metrics.resolve(metric)
+    neighbor_precision = preprocess.resolve_precision(neighbor_precision)
     if metric == _metrics.MANHATTAN:
         raise ValueError("extend_embedding has no Manhattan neighbour search; the metrics it serves are "
                          "'euclidean', 'cosine' and 'correlation'")
@@ -365,7 +379,7 @@ def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repu
         problem.LOGGER.info(f"Computing the {n_neighbors} nearest embedded rows of {n_new} new rows among "
                             f"{n_old}, with max_distance={max_distance}")
     idx, _ = preprocess.cross_nearest_neighbors(new_data, data, n_neighbors, max_distance=max_distance,
-                                                metric=metric, device=device)
+                                                metric=metric, device=device, precision=neighbor_precision)
     listed = idx >= 0
     n_alone = int((~listed.any(1)).sum())
     if n_alone:
@@ -421,11 +435,14 @@ def _approximate_options(approximate_neighbors):
 
 
 def laplacian_embedding(data, embedding_dim=2, n_neighbors=None, max_distance=None, init="quadratic",
-                        device=None, verbose=False, approximate_neighbors=False, metric="euclidean"):
+                        device=None, verbose=False, approximate_neighbors=False, metric="euclidean",
+                        neighbor_precision="float32"):
     """An MDE problem whose solution is a Laplacian embedding [ref: recipes.py:451-503]: the k-NN
     graph of ``preserve_neighbors`` with quadratic penalties, no repulsion and the standardization
-    constraint.  ``data``, ``approximate_neighbors`` and ``metric`` as for ``preserve_neighbors``."""
+    constraint.  ``data``, ``approximate_neighbors``, ``metric`` and ``neighbor_precision`` as for
+    ``preserve_neighbors``."""
     return preserve_neighbors(data, embedding_dim=embedding_dim, attractive_penalty=penalties.Quadratic,
                               repulsive_penalty=None, n_neighbors=n_neighbors, max_distance=max_distance,
                               init=init, device=device, verbose=verbose,
-                              approximate_neighbors=approximate_neighbors, metric=metric)
+                              approximate_neighbors=approximate_neighbors, metric=metric,
+                              neighbor_precision=neighbor_precision)
