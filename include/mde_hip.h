@@ -314,6 +314,34 @@ int64_t mde_knn_bf16_work_bytes(int64_t n_q, int64_t n_c, int32_t nf, int32_t k,
 int mde_knn_bf16(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, const double* mu,
                  int32_t self, int32_t k, int32_t n_cand, int32_t slices, int32_t* idx_out, float* d2_out,
                  void* work, void* stream);
+/* Ranks of listed corpus rows (csrc/mde_knn_rank.hip): for every row i of Q [n_q, nf] and every
+ * entry j = idx[i][c] of its list idx [n_q, m] (int32 rows of C [n_c, nf]; float32, row-major, on the device),
+ * rank_out[i][c] = the number of rows l of C with (d2(i, l), l) < (d2(i, j), j) in lexicographic order: 0-based,
+ * the nearest row has rank 0 and ties go to the smaller index, the order every k-NN kernel lists by.  d2 is the
+ * float32 squared distance of mde_knn / mde_knn_cross / mde_knn_bf16, bit for bit, so the ranks of those
+ * kernels' own lists are 0, 1, ..., k - 1 in every row, duplicate rows and every other tie included.
+ * self != 0: Q == C and n_q == n_c (the self-join); row i itself is not counted, and an entry equal to i is not
+ * ranked.  Entries that are not ranked get rank -1 and d2 FLT_MAX: a negative entry, an entry >= n_c (the
+ * entries live on the device and are not checked on the host; no row is read for them), and with self the row
+ * itself.  d2_out [n_q, m] (may be NULL) receives d2(i, idx[i][c]).  1 <= m <= 64; n_q, n_c < 2^31.
+ * Three launches, no atomics: the thresholds d2(i, j) by the chain of the bf16 search's re-rank; one pass of the
+ * 64x64 Gram tile on the grid of mde_knn_cross (query block, corpus slice) in which every query row counts the
+ * distances that precede each threshold, written to scratch [slices, n_q, m]; a sum over the slices.  Integer
+ * sums: rank_out is identical for every slice count and on every run.  slices as in mde_knn_cross (0: automatic;
+ * 1: the counts go to rank_out directly and the third launch is dropped; 0 <= slices <= 65535).
+ * work: mde_knn_ranks_work_bytes(n_q, n_c, m, slices) bytes of scratch (the row norms of Q and C, the thresholds
+ * and their checked indices, the per-slice counts when there is more than one slice); the call allocates
+ * nothing.  Arguments are checked on the host before any launch: MDE_E_INVALID with a message.
+ * mde_knn_ranks_work_bytes returns a negative MDE_E_* code for invalid arguments (and, with slices == 0, when no
+ * device can be asked for its CU count).  ASYNC. */
+int64_t mde_knn_ranks_work_bytes(int64_t n_q, int64_t n_c, int32_t m, int32_t slices);
+int mde_knn_ranks(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t self, int32_t m,
+                  const int32_t* idx, int32_t slices, int32_t* rank_out, float* d2_out, void* work, void* stream);
+/* count_out[i] (int32 [n]) = the number of entries of row i of a [n, ka] that are >= 0 and occur in row i of
+ * b [n, kb] (int32 neighbour lists on the device; 1 <= ka, kb <= 64): the size of the intersection of two
+ * neighbour lists, an entry that a lists twice counted twice.  ASYNC. */
+int mde_knn_list_overlap(int64_t n, int32_t ka, const int32_t* a, int32_t kb, const int32_t* b, int32_t* count_out,
+                         void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

@@ -248,15 +248,9 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_short_bf16(int n_q, int n_c, 
 }
 
 // The re-rank.  A wave owns one query and a lane one entry of its shortlist (nc <= 64 lanes; -1 is skipped).
-// d2 is what the float32 kernels give the pair: the Gram tile of mde_knn_tile.h sums a dot product as one
-// feature-ordered fmaf chain from 0 (the f32 MFMA rounds once per product, in k order; zero padding adds
-// nothing), so the lane runs that chain over f = 0 .. nf - 1 and forms fmaxf(qn + cn - 2 acc, 0) from the
-// norms of k_row_sqnorm.  (2 acc is exact, so the expression rounds once whether or not it is contracted.)
-// The shortlisted rows are gathered through LDS in chunks of RR_KB features: a half wave reads the 128
-// contiguous bytes of one row per load, and the lane then reads its own row conflict-free (stride 33).  The
-// best k by (d2, index) are placed by rank: a lane counts the entries that precede its own.
-#define RR_KB 32
-#define RR_KBP 33
+// d2 is what the float32 kernels give the pair: knn_wave_pair_d2 (mde_knn_tile.h) runs the Gram tile's
+// feature-ordered fmaf chain on the shortlisted rows, gathered through LDS.  The best k by (d2, index) are
+// placed by rank: a lane counts the entries that precede its own.
 __global__ __launch_bounds__(MDE_BLOCK) void k_knn_rerank(int n_q, int nf, int k, int nc, const float* __restrict__ Q,
                                                           const float* __restrict__ C,
                                                           const float* __restrict__ qn,
@@ -264,8 +258,8 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_rerank(int n_q, int nf, int k
                                                           const int32_t* __restrict__ sidx,
                                                           int32_t* __restrict__ idx_out,
                                                           float* __restrict__ d2_out) {
-  __shared__ float sC[4][64 * RR_KBP];
-  __shared__ float sQ[4][RR_KB];
+  __shared__ float sC[4][64 * KNN_RR_KBP];
+  __shared__ float sQ[4][KNN_RR_KB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t q = (int64_t)blockIdx.x * 4 + wave;
   const int64_t qc = q < n_q ? q : n_q - 1;
@@ -273,31 +267,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_knn_rerank(int n_q, int nf, int k
   const bool valid = mine >= 0;
   const int64_t crow = valid ? mine : 0;
   float* mC = sC[wave];
-  float* mQ = sQ[wave];
-  const int half = lane >> 5, col = lane & 31;
-  float acc = 0.0f;
-  for (int k0 = 0; k0 < nf; k0 += RR_KB) {
-    const int f = k0 + col < nf ? k0 + col : nf - 1;    // clamped: a column past nf is never read back
-    __syncthreads();
-    if (lane < RR_KB) mQ[lane] = Q[qc * nf + f];
-#pragma unroll 8
-    for (int i = 0; i < 32; ++i) {
-      const int r = 2 * i + half;
-      const int64_t src = __shfl((int)crow, r, 64);
-      mC[r * RR_KBP + col] = C[src * nf + f];
-    }
-    __syncthreads();
-    const int kn = nf - k0 < RR_KB ? nf - k0 : RR_KB;
-    const float* my = mC + lane * RR_KBP;
-    if (kn == RR_KB) {
-#pragma unroll
-      for (int kk = 0; kk < RR_KB; ++kk) acc = fmaf(mQ[kk], my[kk], acc);
-    } else {
-      for (int kk = 0; kk < kn; ++kk) acc = fmaf(mQ[kk], my[kk], acc);
-    }
-  }
-  float d2 = SB_FLT_MAX;
-  if (valid) d2 = fmaxf(qn[qc] + cn[crow] - 2.0f * acc, 0.0f);
+  const float d2 = knn_wave_pair_d2(mC, sQ[wave], nf, Q, C, qn, cn, qc, crow, valid);
   const int id = valid ? mine : 0x7fffffff;
   __syncthreads();
   mC[lane] = d2;

@@ -1,7 +1,8 @@
 // mde_knn_tile.h -- the 64x64 Gram tile of the Euclidean k-NN kernels and the pieces around it, written once:
-// k_knn_cross (mde_knn.hip: the exact self-join and the query-against-corpus search) and k_ann_scan
-// (mde_ann.hip) are this tile under different walks over the candidates; k_knn_l1 (mde_metric.hip) has its
-// own VALU tile and shares the lists and the launcher helper.
+// k_knn_cross (mde_knn.hip: the exact self-join and the query-against-corpus search), k_ann_scan
+// (mde_ann.hip) and k_knn_rank (mde_knn_rank.hip) are this tile under different walks over the candidates;
+// k_knn_l1 (mde_metric.hip) has its own VALU tile and shares the lists and the launcher helper.  The same
+// squared distance of single listed pairs, without a tile: knn_wave_pair_d2 at the end.
 //
 // Squared distances are formed as |x|^2 + |y|^2 - 2 x.y with the Gram tile x.y on the f32 matrix cores
 // (v_mfma_f32_32x32x2_f32, exact f32): a 256-thread workgroup owns 64 query rows and takes the candidates
@@ -143,4 +144,47 @@ __device__ __forceinline__ void knn_park_tile(float* sD, const f32x16& acc, Keep
     if (keep(r, c)) d2 = fmaxf(qn(r) + cn(c) - 2.0f * acc[q], 0.0f);
     sD[r * (KNN_BN + 1) + c] = d2;
   }
+}
+
+// The squared distance of listed pairs with the bits the tile gives them (k_knn_rerank of mde_knn_bf16.hip, the
+// thresholds of mde_knn_rank.hip).  A wave owns query row qc of Q and a lane the corpus row crow of C (any
+// readable row where !valid).  The Gram tile sums a dot product as one feature-ordered fmaf chain from 0 (the
+// f32 MFMA rounds once per product, in k order; zero padding adds nothing), so the lane runs that chain over
+// f = 0 .. nf - 1 and forms fmaxf(qn + cn - 2 acc, 0) from the norms of k_row_sqnorm.  (2 acc is exact, so the
+// expression rounds once whether or not it is contracted.)  The listed rows are gathered through LDS in chunks
+// of KNN_RR_KB features: a half wave reads the 128 contiguous bytes of one row per load, and the lane then
+// reads its own row conflict-free (stride 33).  mC [64 * KNN_RR_KBP] and mQ [KNN_RR_KB] are the wave's own
+// LDS; every thread of the workgroup calls (barriers inside).  FLT_MAX where !valid.
+#define KNN_RR_KB 32
+#define KNN_RR_KBP 33
+__device__ __forceinline__ float knn_wave_pair_d2(float* mC, float* mQ, int nf, const float* __restrict__ Q,
+                                                  const float* __restrict__ C, const float* __restrict__ qn,
+                                                  const float* __restrict__ cn, int64_t qc, int64_t crow,
+                                                  bool valid) {
+  const int lane = threadIdx.x & 63;
+  const int half = lane >> 5, col = lane & 31;
+  float acc = 0.0f;
+  for (int k0 = 0; k0 < nf; k0 += KNN_RR_KB) {
+    const int f = k0 + col < nf ? k0 + col : nf - 1;    // clamped: a column past nf is never read back
+    __syncthreads();
+    if (lane < KNN_RR_KB) mQ[lane] = Q[qc * nf + f];
+#pragma unroll 8
+    for (int i = 0; i < 32; ++i) {
+      const int r = 2 * i + half;
+      const int64_t src = __shfl((int)crow, r, 64);
+      mC[r * KNN_RR_KBP + col] = C[src * nf + f];
+    }
+    __syncthreads();
+    const int kn = nf - k0 < KNN_RR_KB ? nf - k0 : KNN_RR_KB;
+    const float* my = mC + lane * KNN_RR_KBP;
+    if (kn == KNN_RR_KB) {
+#pragma unroll
+      for (int kk = 0; kk < KNN_RR_KB; ++kk) acc = fmaf(mQ[kk], my[kk], acc);
+    } else {
+      for (int kk = 0; kk < kn; ++kk) acc = fmaf(mQ[kk], my[kk], acc);
+    }
+  }
+  float d2 = 3.402823466e+38f;
+  if (valid) d2 = fmaxf(qn[qc] + cn[crow] - 2.0f * acc, 0.0f);
+  return d2;
 }
