@@ -342,6 +342,33 @@ int mde_knn_ranks(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const fl
  * neighbour lists, an entry that a lists twice counted twice.  ASYNC. */
 int mde_knn_list_overlap(int64_t n, int32_t ka, const int32_t* a, int32_t kb, const int32_t* b, int32_t* count_out,
                          void* stream);
+/* Sums over all pairs of the distances in two spaces (csrc/mde_pair_moments.hip): what the
+ * stress, the distance correlation and the Shepard histogram of pymde_amd.quality are computed from.
+ * A [n, nfa] and B [n, nfb] (float32, row-major, on the device) hold the same n rows in two spaces; q_rows int32
+ * [n_q] on the device lists the query rows (NULL: all n rows in order, n_q == n; an entry outside [0, n) is the
+ * caller's error and is not checked).  For every query i = q_rows[r] and every row j != i (by index: a duplicate of
+ * row i elsewhere counts) D = dist_A(i, j) and E = dist_B(i, j), with dist = sqrtf(d2) for mode 0 and 0.5f * d2
+ * for mode 1 (the cosine / correlation distance of unit rows), d2 the float32 squared distance of mde_knn.
+ * mde_pair_moments: row_sums double [n_q, 5] = the sums over j of D, E, D^2, E^2, D E (accumulated in double, the
+ * products formed in double from the float32 D and E); row_max float [n_q, 2] = the row's largest D and E;
+ * totals double [8] = the five sums over all rows, the largest D, the largest E, the pair count n_q (n - 1).
+ * No floating-point atomics and a fixed order: for a given slice count the result is the same bits on every run,
+ * and a row's sums do not depend on which other queries are listed.  Different slice counts differ by rounding.
+ * mde_pair_histogram: every pair with a_lo <= D <= a_hi and b_lo <= E <= b_hi adds one to counts[bd][be],
+ * bd = min(bins - 1, (int)((D - a_lo) * s_a)) with s_a = (float)bins / (a_hi - a_lo), be likewise; counts int64
+ * [bins, bins] on the device is added to, so the caller zeroes it.  1 <= bins <= 64.  Integer atomics only: the
+ * counts are the same for every slice count and on every run.
+ * Both walk the grid of mde_knn_ranks (query block, corpus slice; slices as there, 0: automatic) with two Gram
+ * tiles per step.  work: mde_pair_moments_work_bytes(n, n_q, slices) bytes of scratch for either call (the row
+ * norms, the per-slice sums); the calls allocate nothing.  2 <= n < 2^31, 1 <= n_q < 2^31.  Arguments are checked
+ * on the host before any launch: MDE_E_INVALID with a message.  ASYNC. */
+int64_t mde_pair_moments_work_bytes(int64_t n, int64_t n_q, int32_t slices);
+int mde_pair_moments(int64_t n, int32_t nfa, const float* A, int32_t mode_a, int32_t nfb, const float* B,
+                     int32_t mode_b, int64_t n_q, const int32_t* q_rows, int32_t slices, double* row_sums,
+                     float* row_max, double* totals, void* work, void* stream);
+int mde_pair_histogram(int64_t n, int32_t nfa, const float* A, int32_t mode_a, int32_t nfb, const float* B,
+                       int32_t mode_b, int64_t n_q, const int32_t* q_rows, int32_t slices, int32_t bins, float a_lo,
+                       float a_hi, float b_lo, float b_hi, int64_t* counts, void* work, void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

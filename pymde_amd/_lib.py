@@ -88,6 +88,11 @@ SYMBOLS = {
     "mde_knn_ranks_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "mde_knn_ranks": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_knn_list_overlap": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "mde_pair_moments_work_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "mde_pair_moments": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp]),
+    "mde_pair_histogram": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_i32, c_i32, c_f32,
+                                   c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "mde_ann_search": (c_i32, [c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
                                c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_ann_centroids": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),

@@ -8,10 +8,19 @@ neighbours in the data that the embedding tore apart lower the continuity.  skle
 n x n distance matrix and an argsort per row; here a rank is a count over one pass of the Gram tile of the
 exact k-NN search, so the scores cost about as much as the searches they are built on and need O(n k) memory.
 
+Those are rank statistics of the nearest few rows.  Whether far things stay far is what the global scores at the
+end of this module tell: Kruskal's ``stress``, the ``distance_correlation`` of all pairwise distances and the
+``shepard_histogram``, all functions of sums over every pair that one more pass of the same Gram tile forms in
+O(n) memory (``pair_moments``, ``csrc/mde_pair_moments.hip``).
+
 A rank is 0-based and ties go to the smaller index: ``rank(i, j)`` is the number of rows ``l`` (other than
 ``i`` in a self-join) with ``(d2(i, l), l) < (d2(i, j), j)``, where ``d2`` is the float32 squared distance of
 the Euclidean k-NN kernels, bit for bit.  The ranks of a search's own lists are therefore ``0 .. k - 1``.
 """
+import collections
+import math
+
+import numpy as np
 import torch
 
 from pymde_amd import _lib, util
@@ -238,3 +247,244 @@ def neighbor_overlap(data, X, n_neighbors=15, metric="euclidean", per_item=False
     if not per_item:
         return score
     return score, (count.to(torch.float64) / k).to(torch.float32)
+
+
+# ---------------------------------------------------------------- global scores: all pairs, not the nearest few
+# (csrc/mde_pair_moments.hip)
+MAX_BINS = 64          # PAIR_MAX_BINS of csrc/mde_pair_moments.hip
+
+PairMoments = collections.namedtuple(
+    "PairMoments", ["count", "sum_d", "sum_e", "sum_dd", "sum_ee", "sum_de", "max_d", "max_e", "row_sums", "rows"])
+PairMoments.__doc__ = """Sums over the counted pairs (i, j), j != i, of the data distance D and the embedding distance
+E: ``count`` pairs; ``sum_d``, ``sum_e``, ``sum_dd``, ``sum_ee``, ``sum_de`` (Python floats, summed in float64 on
+the GPU); ``max_d``, ``max_e`` the largest D and E; ``row_sums`` float64 [n_q, 5] on the GPU, every query row's own
+five sums in that order; ``rows`` int64 [n_q] on the CPU, the sampled query rows (None: every row, in order)."""
+
+
+def _pair_modes(metric):
+    """(mode_a, mode_b) of ``mde_pair_moments``: the data side returns ``0.5 d2`` of the unit rows for cosine /
+    correlation (the distance the searches return), the embedding side is always Euclidean."""
+    return (0 if metric == _metrics.EUCLIDEAN else 1), 0
+
+
+def _pair_work(lib, n, n_q, slices, device):
+    nbytes = int(lib.mde_pair_moments_work_bytes(n, n_q, slices))
+    if nbytes < 0:
+        _lib.check(nbytes)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _pair_moments(A, B, mode_a=0, mode_b=0, q_rows=None, slices=0):
+    """``mde_pair_moments`` on prepared dense float32 matrices (and an int32 list of query rows) on one GPU:
+    ``(row_sums float64 [n_q, 5], row_max float32 [n_q, 2], totals float64 [8])`` on that GPU."""
+    n, device = int(A.shape[0]), A.device
+    n_q = n if q_rows is None else int(q_rows.shape[0])
+    lib = _lib.load()
+    row_sums = torch.empty((n_q, 5), dtype=torch.float64, device=device)
+    row_max = torch.empty((n_q, 2), dtype=torch.float32, device=device)
+    totals = torch.empty(8, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        work = _pair_work(lib, n, n_q, slices, device)
+        _lib.check(lib.mde_pair_moments(n, int(A.shape[1]), _lib.ptr(A), mode_a, int(B.shape[1]), _lib.ptr(B), mode_b,
+                                        n_q, _lib.ptr(q_rows), slices, _lib.ptr(row_sums), _lib.ptr(row_max),
+                                        _lib.ptr(totals), _lib.ptr(work), _lib.stream_ptr(device)))
+    return row_sums, row_max, totals
+
+
+def _pair_histogram(A, B, bins, a_range, b_range, mode_a=0, mode_b=0, q_rows=None, slices=0):
+    """``mde_pair_histogram`` on prepared matrices: int64 [bins, bins] on their GPU."""
+    n, device = int(A.shape[0]), A.device
+    n_q = n if q_rows is None else int(q_rows.shape[0])
+    lib = _lib.load()
+    counts = torch.zeros((bins, bins), dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        work = _pair_work(lib, n, n_q, slices, device)
+        _lib.check(lib.mde_pair_histogram(n, int(A.shape[1]), _lib.ptr(A), mode_a, int(B.shape[1]), _lib.ptr(B),
+                                          mode_b, n_q, _lib.ptr(q_rows), slices, bins, a_range[0], a_range[1],
+                                          b_range[0], b_range[1], _lib.ptr(counts), _lib.ptr(work),
+                                          _lib.stream_ptr(device)))
+    return counts
+
+
+def _check_global(data, X, metric, sample, slices=0):
+    """The argument checks the global scores share, before any device is required: (metric, n, m) with ``m`` the
+    number of sampled query rows, None for all of them."""
+    metric = _resolve_metric(metric, data, X)
+    _check_matrix(data, "data")
+    _check_matrix(X, "X")
+    n = int(data.shape[0])
+    if int(X.shape[0]) != n:
+        raise ValueError(f"`data` has {n} rows and the embedding `X` has {int(X.shape[0])}; they must agree")
+    if n < 2 or int(data.shape[1]) < 1 or int(X.shape[1]) < 1:
+        raise ValueError("`data` and `X` need at least two rows and one feature")
+    if not 0 <= int(slices) <= MAX_SLICES:
+        raise ValueError(f"slices must lie in [0, {MAX_SLICES}] (0: automatic), got {slices}")
+    if sample is not None:
+        if isinstance(sample, bool) or int(sample) != sample or not 1 <= int(sample) <= n:
+            raise ValueError(f"sample must be None or a whole number of query rows in [1, {n}], got {sample!r}")
+        sample = int(sample) if int(sample) < n else None
+    return metric, n, sample
+
+
+def _check_scale(scale):
+    if isinstance(scale, str):
+        if scale != "optimal":
+            raise ValueError(f"scale must be 'optimal' or a positive finite number, got {scale!r}")
+        return scale
+    try:
+        value = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"scale must be 'optimal' or a positive finite number, got {scale!r}") from None
+    if isinstance(scale, bool) or not (value > 0.0 and math.isfinite(value)):
+        raise ValueError(f"scale must be 'optimal' or a positive finite number, got {scale!r}")
+    return value
+
+
+def _check_bins(bins):
+    if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= MAX_BINS:
+        raise ValueError(f"bins must be a whole number in [1, {MAX_BINS}], got {bins!r}")
+    return int(bins)
+
+
+def _check_range(range_):
+    """``((d_lo, d_hi), (e_lo, e_hi))`` as float32-representable floats, or None."""
+    if range_ is None:
+        return None
+    message = f"range must be None or ((d_lo, d_hi), (e_lo, e_hi)) with finite lo < hi, got {range_!r}"
+    try:
+        (d_lo, d_hi), (e_lo, e_hi) = range_
+        out = tuple(float(torch.tensor(float(v), dtype=torch.float32)) for v in (d_lo, d_hi, e_lo, e_hi))
+    except (TypeError, ValueError):
+        raise ValueError(message) from None
+    if not all(math.isfinite(v) for v in out) or not (out[0] < out[1] and out[2] < out[3]):
+        raise ValueError(message)
+    return (out[0], out[1]), (out[2], out[3])
+
+
+def _sample_rows(n, m, seed):
+    """``m`` distinct rows of ``range(n)`` from a ``torch.Generator`` seeded with ``seed`` (int64, on the CPU)."""
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    return torch.randperm(n, generator=g)[:m].contiguous()
+
+
+def _prepared_pair(data, X, metric, m, seed):
+    """The two matrices as ``trustworthiness`` prepares them, on one GPU, and the sampled rows:
+    (A, B, rows int64 on the CPU or None, q_rows int32 on the GPU or None)."""
+    device = _device_of(X, data)
+    A = _self_rows(data, metric, device, "data")
+    B = _self_rows(X, _metrics.EUCLIDEAN, device, "X")
+    if m is None:
+        return A, B, None, None
+    rows = _sample_rows(int(A.shape[0]), m, seed)
+    return A, B, rows, rows.to(device=device, dtype=torch.int32)
+
+
+def pair_moments(data, X, metric="euclidean", sample=None, seed=0, slices=0):
+    """The sums every global score here is a function of: over all pairs (i, j), j != i, of the distance D in
+    ``data`` [n, n_features] under ``metric`` and the Euclidean distance E in the embedding ``X`` [n, d], the sums
+    of D, E, D^2, E^2 and D E, the two maxima and the pair count (a ``PairMoments``).  One pass of the Gram tile of
+    the exact k-NN search over both matrices: O(n) memory, about the cost of one exact search of ``data``.
+
+    ``data``, ``X`` and ``metric`` as in ``trustworthiness``, and prepared the same way; for ``"cosine"`` and
+    ``"correlation"`` D is ``1 - cos``, the distance the searches return.  Each distance is the float32 distance
+    of the k-NN kernels; the sums are float64, in a fixed order, the same bits on every run (for one ``slices``,
+    the corpus split of the kernel's grid; 0: automatic -- another split changes the last bits).
+
+    ``sample=m`` (``1 <= m <= n``): ``m`` distinct query rows, drawn with a ``torch.Generator`` seeded with
+    ``seed``, against all ``n`` rows -- ``m (n - 1)`` ordered pairs, an unbiased estimate of every mean at
+    ``m / n`` of the cost.  ``None``: every row, all ``n (n - 1)`` ordered pairs (each unordered pair twice).
+    Manhattan and ``Graph`` inputs are a ``ValueError``."""
+    metric, n, m = _check_global(data, X, metric, sample, slices)
+    A, B, rows, q_rows = _prepared_pair(data, X, metric, m, seed)
+    row_sums, _, totals = _pair_moments(A, B, *_pair_modes(metric), q_rows=q_rows, slices=int(slices))
+    t = totals.cpu().tolist()
+    return PairMoments(int(round(t[7])), t[0], t[1], t[2], t[3], t[4], t[5], t[6], row_sums, rows)
+
+
+Scores = collections.namedtuple("Scores", ["stress", "alpha", "correlation", "per_item"])
+
+
+def _scores_from_moments(moments, scale="optimal", per_item=False):
+    """Every score as a float64 function of a ``PairMoments`` (no GPU needed): ``Scores(stress, alpha,
+    correlation, per_item)``.
+
+    ``stress``: Kruskal's stress-1 ``sqrt(sum (D - alpha E)^2 / sum D^2)``.  ``scale="optimal"``: the ``alpha =
+    sum D E / sum E^2`` that minimises it, for which it is ``sqrt(max(0, 1 - (sum D E)^2 / (sum D^2 sum E^2)))``;
+    a number: that ``alpha``, through ``sum D^2 - 2 alpha sum D E + alpha^2 sum E^2``.  Both forms subtract
+    nearly equal numbers when the stress is small: of a stress ``s`` about ``1e-16 / s^2`` relative digits are
+    lost, so values below ~1e-4 mean "zero" (the float32 distances put their own floor at ~1e-3 to 1e-4).
+    ``correlation``: Pearson's r of D and E over the counted pairs.  ``per_item``: float32, one value per query
+    row -- the row's ``sum_j (D - alpha E)^2`` over its ``sum_j D^2``, square-rooted, with the global ``alpha``
+    (on the device of ``moments.row_sums``); NaN for a row whose D are all zero.
+    No pairs, or a space in which every distance is zero, has no stress / correlation: NaN."""
+    scale = _check_scale(scale)
+    c = float(moments.count)
+    sd, se, sdd, see, sde = (float(moments.sum_d), float(moments.sum_e), float(moments.sum_dd),
+                             float(moments.sum_ee), float(moments.sum_de))
+    nan = float("nan")
+    if scale == "optimal":
+        alpha = sde / see if see > 0.0 else nan
+        stress = math.sqrt(max(0.0, 1.0 - (sde * sde) / (sdd * see))) if sdd > 0.0 and see > 0.0 else nan
+    else:
+        alpha = scale
+        stress = math.sqrt(max(0.0, sdd - 2.0 * alpha * sde + alpha * alpha * see) / sdd) if sdd > 0.0 else nan
+    var_d, var_e = c * sdd - sd * sd, c * see - se * se
+    correlation = (c * sde - sd * se) / math.sqrt(var_d * var_e) if var_d > 0.0 and var_e > 0.0 else nan
+    rows = None
+    if per_item:
+        s = moments.row_sums.to(torch.float64)
+        rows = ((s[:, 2] - 2.0 * alpha * s[:, 4] + alpha * alpha * s[:, 3]).clamp_(min=0.0) / s[:, 2]).sqrt_()
+        rows = rows.to(torch.float32)
+    return Scores(stress, alpha, correlation, rows)
+
+
+def stress(data, X, scale="optimal", per_item=False, metric="euclidean", sample=None, seed=0):
+    """Kruskal's normalised stress (stress-1) of the embedding ``X`` of ``data``: ``sqrt(sum (D - alpha E)^2 /
+    sum D^2)`` over all pairs, D the distance in ``data`` under ``metric`` and E the Euclidean distance in ``X``.
+    0 for an embedding that keeps every distance (up to ``alpha``); it sees the far pairs that
+    ``trustworthiness`` and ``continuity`` do not.
+
+    ``scale="optimal"``: ``alpha = sum D E / sum E^2``, the factor that minimises the stress, which makes it
+    invariant to the scale of the embedding -- right for ``Standardized`` and ``preserve_neighbors`` embeddings.
+    ``scale=<number>``: that ``alpha``; 1.0 takes ``preserve_distances`` at its word.  Near zero the formula
+    loses half its digits (``_scores_from_moments``): an exact copy scores ~1e-4 or less, not 0.0 exactly unless
+    the two matrices are the same bits.  Other arguments as in ``pair_moments``.
+
+    Returns a Python float; ``per_item=True`` returns ``(stress, per_row)`` with ``per_row`` float32 [n_q] on
+    the GPU, every query row's own stress under the same ``alpha`` (colour a plot by it; with ``sample`` the
+    rows are ``pair_moments(...).rows``, drawn from the same ``seed``)."""
+    _check_scale(scale)
+    scores = _scores_from_moments(pair_moments(data, X, metric, sample, seed), scale, per_item)
+    return (scores.stress, scores.per_item) if per_item else scores.stress
+
+
+def distance_correlation(data, X, metric="euclidean", sample=None, seed=0):
+    """Pearson's correlation of the pairwise distances in ``data`` (under ``metric``) and in the embedding ``X``
+    over all pairs -- the number behind a Shepard diagram; 1.0 when the embedding distances are an increasing
+    linear function of the data distances.  This is NOT Szekely's distance correlation (dCor, the statistic of
+    independence built from doubly centred distance matrices), only the plain correlation coefficient of two
+    lists of distances.  Arguments as in ``pair_moments``; a Python float."""
+    return _scores_from_moments(pair_moments(data, X, metric, sample, seed)).correlation
+
+
+def shepard_histogram(data, X, bins=64, range=None, metric="euclidean", sample=None, seed=0):
+    """The Shepard diagram as a 2-D histogram: ``(counts, d_edges, e_edges, n_counted)`` with ``counts`` int64
+    [bins, bins] on the GPU -- ``counts[a, b]`` pairs whose data distance D falls in bin ``a`` and whose
+    embedding distance E in bin ``b`` -- the float64 numpy arrays of the ``bins + 1`` bin edges on each axis, and
+    the number of pairs counted.  ``1 <= bins <= 64``; the bins are uniform, the last one closed on the right, as
+    in ``numpy.histogram2d``, with the bin of a value computed in float32.
+
+    ``range=((d_lo, d_hi), (e_lo, e_hi))``: a pair outside either interval is not counted (``n_counted`` tells).
+    ``None``: ``[0, max D] x [0, max E]`` from a ``pair_moments`` pass first, so every pair is counted.  Other
+    arguments as in ``pair_moments``."""
+    bins, range_ = _check_bins(bins), _check_range(range)
+    metric, n, m = _check_global(data, X, metric, sample)
+    A, B, rows, q_rows = _prepared_pair(data, X, metric, m, seed)
+    modes = _pair_modes(metric)
+    if range_ is None:
+        top = _pair_moments(A, B, *modes, q_rows=q_rows)[2][5:7].cpu().tolist()
+        range_ = tuple((0.0, v if v > 0.0 else 1.0) for v in top)   # a space whose distances are all zero: one unit
+    counts = _pair_histogram(A, B, bins, range_[0], range_[1], *modes, q_rows=q_rows)
+    d_edges, e_edges = (np.linspace(lo, hi, bins + 1, dtype=np.float64) for lo, hi in range_)
+    return counts, d_edges, e_edges, int(counts.sum().item())
