@@ -369,6 +369,32 @@ int mde_pair_moments(int64_t n, int32_t nfa, const float* A, int32_t mode_a, int
 int mde_pair_histogram(int64_t n, int32_t nfa, const float* A, int32_t mode_a, int32_t nfb, const float* B,
                        int32_t mode_b, int64_t n_q, const int32_t* q_rows, int32_t slices, int32_t bins, float a_lo,
                        float a_hi, float b_lo, float b_hi, int64_t* counts, void* work, void* stream);
+/* The loss and gradient of a dense MDE problem (csrc/mde_pair_loss.hip): a loss over all
+ * P = n (n - 1) / 2 pairs of n items without an edge list, what pymde_amd.DenseMDE minimises.
+ * X [n, d] (float32, row-major, on the device; 1 <= d <= 8) is the embedding.  The original deviation D(i, j) of a
+ * pair comes from exactly one of two sources (the other pointer is NULL):
+ *   A [n, nf]   the prepared data rows: D = d_scale * dist_A(i, j), dist_A as in mde_pair_moments (mode 0 sqrtf(d2),
+ *               mode 1 0.5f * d2), bit for bit the distances of that call;
+ *   Dm [n, n]   a row-major float32 matrix of deviations: D = d_scale * Dm[i][j] (nf and mode are ignored).  Dm is
+ *               expected to be symmetric, non-negative and finite; it is not checked, an entry equal to FLT_MAX is
+ *               skipped, and the diagonal is never used.
+ * For every row i and every j != i (by index): E = |x_i - x_j| from the differences, and (l, l'(E) / E) of the loss
+ * `kind` (one of MDE_F_L_*; scalars s0, s1, s2 as in struct mde_func) at a0 = D and, for the weighted kinds,
+ * a1 = 1 / D^2 (the losses' default weights), with the NaN / Inf -> 1 rule of mde_average_distortion on l'(E) / E.
+ *   row_loss double [n]   = sum_j l(E_ij, D_ij)
+ *   grad float [n, d]     = (1 / P) sum_j (l'(E_ij) / E_ij) (x_i - x_j)
+ *   loss double [1]       = sum_i row_loss[i] / (2 P)
+ * which are the average distortion of the edge-list problem over all_edges(n), its gradient, and the sum of the
+ * distortions of the pairs of every item.  Sums in double; no floating-point atomics and a fixed order: for a given
+ * slice count the three outputs are the same bits on every run; different slice counts differ by rounding.
+ * The grid is that of mde_pair_moments (row block, column slice; slices as there, 0: automatic).
+ * work: mde_pair_loss_work_bytes(n, d, slices) bytes of scratch (the per-slice partials, the row norms of A); the
+ * call allocates nothing.  2 <= n < 2^31; d_scale positive and finite.  Arguments are checked on the host before
+ * any launch: MDE_E_INVALID with a message.  ASYNC. */
+int64_t mde_pair_loss_work_bytes(int64_t n, int32_t d, int32_t slices);
+int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale, int32_t d,
+                  const float* X, int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
+                  float* grad, double* row_loss, void* work, void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

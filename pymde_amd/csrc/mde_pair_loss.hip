@@ -1,0 +1,254 @@
+// mde_pair_loss.hip -- the loss and the gradient of a DENSE MDE problem: a loss of pymde_amd.losses
+// over ALL n (n - 1) / 2 pairs without an edge list, what pymde_amd.DenseMDE minimises, in O(n) memory beside D.
+//
+// For every row i and every row j != i (by index: a duplicate of row i elsewhere counts)
+//   E = |x_i - x_j| from the differences (never |x|^2 + |y|^2 - 2 x.y: the gradient multiplies f'(E) / E by x_i - x_j,
+//       and the expansion cancels for close points, exactly where f'(E) / E is large),
+//   D = d_scale * the original deviation of the pair, from one of two sources:
+//       Gram     the 64x64 Gram tile of the prepared data rows A [n, nf] (mde_knn_tile.h), parked as squared distances,
+//                through pair_dist(d2, mode): bit for bit the D of mde_pair_moments;
+//       matrix   a 64x64 tile of a row-major float32 [n, n] matrix, parked in the same LDS block (a wave reads whole
+//                256-byte row segments; 64-bit offsets);
+//   (l, gd) = mde_eval_rt(kind, E^2, a0 = D, a1 = 1 / D^2, scalars), gd = l'(E) / E under the reference's
+//       NaN / Inf -> 1 rule (mde_fix_g),
+//   row_loss[i] = sum_j l,  G[i, :] = sum_j gd (x_i - x_j),  loss = sum_i row_loss[i] / (2 P),  grad = G / P,
+//   P = n (n - 1) / 2: MDE(n, d, all_edges(n), loss(deviations)).average_distortion and its gradient.
+//
+//   k_pair_loss_walk   the grid of k_pair_walk: workgroup (x, y) owns 64 rows and the column tiles of slice y.  Per
+//                      tile the D side is parked in sD and the 64 column rows of X are staged as [64][DC] floats
+//                      (DC = d padded with zeros to 1, 2, 3 or 8); thread t owns tile row t & 63, kept in registers,
+//                      and the 16 columns 16 (t >> 6) ...: the lanes of a wave read the same staged column (a
+//                      broadcast) and 64 rows of sD at stride 65 (conflict-free).  1 + DC double accumulators per
+//                      thread, every product formed in double from its float32 terms; the four threads of a row are
+//                      combined in thread order.  No floating-point atomics.
+//   k_pair_loss_fold   adds the per-slice partials in slice order: row_loss, and grad = G / P rounded once
+//   k_pair_loss_total  one workgroup reduces row_loss to the loss in a fixed order
+// For a given slice count the loss, the gradient and row_loss are the same bits on every run.
+#include <math.h>
+
+#include "mde_pair.h"
+#include "mde_functions.h"
+
+#define PAIR_LOSS_MAX_D 8
+#define PAIR_LOSS_XS (KNN_BN * PAIR_LOSS_MAX_D)   // floats of the staged column rows of X: 2 KB
+
+template <int DC, bool MATRIX>
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n, int nf, int d, int mode, int64_t slice_cols,
+                                                              const float* __restrict__ A,
+                                                              const float* __restrict__ an,
+                                                              const float* __restrict__ Dm,
+                                                              const float* __restrict__ X, int kind, int weighted,
+                                                              MdeScalars S, float d_scale,
+                                                              double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const knn_tile_lds s = knn_tile_carve(lds, 0, PAIR_TILE + PAIR_LOSS_XS);
+  float* sX = s.extra + PAIR_TILE;                              // [KNN_BN][DC]
+  const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
+  const int64_t lo = (int64_t)blockIdx.y * slice_cols;
+  const int64_t c_lo = lo < n ? lo : n, c_hi = lo + slice_cols < n ? lo + slice_cols : n;
+  float xi[DC];                                                 // the thread's own row
+#pragma unroll
+  for (int k = 0; k < DC; ++k) xi[k] = (row0 + r < n && k < d) ? X[(row0 + r) * d + k] : 0.0f;
+  const float* arow[KNN_STG];
+  bool qok[KNN_STG];
+  if constexpr (!MATRIX) {
+#pragma unroll
+    for (int q = 0; q < KNN_STG; ++q) {
+      const int64_t gr = row0 + (tid >> 5) + 8 * q;
+      qok[q] = gr < n;
+      arow[q] = A + (qok[q] ? gr : 0) * nf;
+    }
+  }
+  double sl = 0.0, sg[DC];
+#pragma unroll
+  for (int k = 0; k < DC; ++k) sg[k] = 0.0;
+  for (int64_t col0 = c_lo; col0 < c_hi; col0 += KNN_BN) {
+    auto keep = [&](int rr, int cc) { return row0 + rr < n && col0 + cc < n && row0 + rr != col0 + cc; };
+    if constexpr (MATRIX) {
+      // wave w takes the tile rows w, w + 4, ...: all sixteen loads go out from clamped addresses before the first is
+      // used, and what the tile does not have (or the diagonal) is replaced when the registers are parked
+      const int lane = tid & 63;
+      const int64_t gc = col0 + lane < n ? col0 + lane : n - 1;
+      float v[KNN_BM / 4];
+#pragma unroll
+      for (int q = 0; q < KNN_BM / 4; ++q) {
+        const int64_t gr = row0 + w + 4 * q < n ? row0 + w + 4 * q : n - 1;
+        v[q] = Dm[gr * (int64_t)n + gc];
+      }
+      __syncthreads();                                          // the walk of the last tile is over
+#pragma unroll
+      for (int q = 0; q < KNN_BM / 4; ++q)
+        s.sD[(w + 4 * q) * (KNN_BN + 1) + lane] = keep(w + 4 * q, lane) ? v[q] : PAIR_FLT_MAX;
+    } else {
+      const float* acol[KNN_STG];
+      bool cok[KNN_STG];
+#pragma unroll
+      for (int q = 0; q < KNN_STG; ++q) {
+        const int64_t gc = col0 + (tid >> 5) + 8 * q;
+        cok[q] = gc < n;
+        acol[q] = A + (cok[q] ? gc : n - 1) * nf;
+      }
+      // the park follows the barriers of knn_gram_tile: every thread is past the walk of the last tile by then
+      const f32x16 acc = knn_gram_tile(s.sA, s.sB, nf, arow, qok, acol, cok);
+      knn_park_tile(s.sD, acc, keep, [&](int rr) { return an[row0 + rr]; }, [&](int cc) { return an[col0 + cc]; });
+    }
+    for (int i = tid; i < KNN_BN * DC; i += MDE_BLOCK) {
+      const int c = i / DC, k = i - c * DC;
+      sX[i] = (col0 + c < n && k < d) ? X[(col0 + c) * d + k] : 0.0f;
+    }
+    __syncthreads();
+    const float* pd = s.sD + r * (KNN_BN + 1) + w * PAIR_COLS;
+    const float* px = sX + w * PAIR_COLS * DC;
+#pragma unroll 4
+    for (int cc = 0; cc < PAIR_COLS; ++cc) {
+      const float v = pd[cc];
+      if (v != PAIR_FLT_MAX) {                                  // what keep() refused is parked as FLT_MAX
+        const float D = (MATRIX ? v : pair_dist(v, mode)) * d_scale;
+        float diff[DC], ss = 0.0f;
+#pragma unroll
+        for (int k = 0; k < DC; ++k) {
+          diff[k] = xi[k] - px[cc * DC + k];
+          ss = fmaf(diff[k], diff[k], ss);
+        }
+        const float a1 = weighted ? 1.0f / (D * D) : 0.0f;      // the losses' default weights
+        float f, gd;
+        mde_eval_rt(kind, ss, D, a1, S, f, gd);
+        gd = mde_fix_g(gd);
+        sl += (double)f;
+#pragma unroll
+        for (int k = 0; k < DC; ++k) sg[k] = fma((double)gd, (double)diff[k], sg[k]);
+      }
+    }
+  }
+  __syncthreads();                                              // the last walk is over: sD and the tile after it are free
+  constexpr int NV = 1 + DC;
+  double* cs = reinterpret_cast<double*>(s.sD);                 // [4][KNN_BM][NV]; sD starts at a multiple of 8 bytes
+  double* mine = cs + ((size_t)w * KNN_BM + r) * NV;
+  mine[0] = sl;
+#pragma unroll
+  for (int k = 0; k < DC; ++k) mine[1 + k] = sg[k];
+  __syncthreads();
+  // thread (row, v) adds value v of the row's four threads in thread order
+  for (int i = tid; i < KNN_BM * NV; i += MDE_BLOCK) {
+    const int rr = i / NV, v = i - NV * rr;
+    if (row0 + rr < n && v <= d) {
+      double t = cs[((size_t)0 * KNN_BM + rr) * NV + v];
+#pragma unroll
+      for (int u = 1; u < 4; ++u) t += cs[((size_t)u * KNN_BM + rr) * NV + v];
+      part[((int64_t)blockIdx.y * n + row0 + rr) * (1 + d) + v] = t;
+    }
+  }
+}
+static_assert(4 * KNN_BM * (1 + PAIR_LOSS_MAX_D) * sizeof(double) <= 2 * PAIR_TILE * sizeof(float),
+              "the row partials must fit in the parked tile and the tile after it");
+
+// row_loss[i] and grad[i, :] = G[i, :] / P from the per-slice partials [slices, n, 1 + d], added in slice order.
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold(int64_t n, int d, int slices, double pairs,
+                                                              const double* __restrict__ part,
+                                                              double* __restrict__ row_loss,
+                                                              float* __restrict__ grad) {
+  const int64_t total = n * (1 + d);
+  for (int64_t i = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * MDE_BLOCK) {
+    double t = 0.0;
+    for (int y = 0; y < slices; ++y) t += part[(int64_t)y * total + i];
+    const int64_t row = i / (1 + d);
+    const int v = (int)(i - row * (1 + d));
+    if (v == 0)
+      row_loss[row] = t;
+    else
+      grad[row * d + v - 1] = (float)(t / pairs);
+  }
+}
+
+// One workgroup: thread t adds the rows t, t + 256, ... in row order, thread 0 then adds the 256 threads' sums in
+// thread order.  loss = sum_i row_loss[i] / (2 P): every pair is in two rows.
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_total(int64_t n, double pairs,
+                                                               const double* __restrict__ row_loss,
+                                                               double* __restrict__ loss) {
+  __shared__ double sums[MDE_BLOCK];
+  double t = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += MDE_BLOCK) t += row_loss[i];
+  sums[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = sums[0];
+    for (int u = 1; u < MDE_BLOCK; ++u) a += sums[u];
+    loss[0] = a / (2.0 * pairs);
+  }
+}
+
+static bool pair_loss_kind_ok(int32_t kind) { return kind >= MDE_F_L_QUADRATIC && kind <= MDE_F_L_LOG1P; }
+static bool pair_loss_args_ok(int64_t n, int32_t d, int32_t slices) {
+  return pair_args_ok(n, n, slices) && d >= 1 && d <= PAIR_LOSS_MAX_D;
+}
+
+// work: [s, n, 1 + d] doubles | the row norms of A, [n] floats (the Gram source; the room is there for either source)
+extern "C" int64_t mde_pair_loss_work_bytes(int64_t n, int32_t d, int32_t slices) {
+  if (!pair_loss_args_ok(n, d, slices)) {
+    mde_set_error("mde_pair_loss_work_bytes: invalid arguments (2 <= n < 2^31, 1 <= d <= %d, 0 <= slices <= %d)",
+                  PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+    return MDE_E_INVALID;
+  }
+  const int64_t s = cross_resolve_slices(n, n, slices);
+  if (s < 0) return s;
+  return s * n * (1 + d) * 8 + 4 * n;
+}
+
+template <int DC>
+static void pair_loss_launch(bool matrix, dim3 grid, hipStream_t st, int n, int nf, int d, int mode, int64_t slice_cols,
+                             const float* A, const float* an, const float* Dm, const float* X, int kind,
+                             MdeScalars S, float d_scale, double* part) {
+  const size_t lds = knn_tile_lds_bytes(0, PAIR_TILE + PAIR_LOSS_XS);
+  const int weighted = kind == MDE_F_L_WEIGHTED_QUADRATIC || kind == MDE_F_L_WEIGHTED_POWER;
+  if (matrix)
+    hipLaunchKernelGGL((k_pair_loss_walk<DC, true>), grid, dim3(MDE_BLOCK), lds, st, n, nf, d, mode, slice_cols, A, an,
+                       Dm, X, kind, weighted, S, d_scale, part);
+  else
+    hipLaunchKernelGGL((k_pair_loss_walk<DC, false>), grid, dim3(MDE_BLOCK), lds, st, n, nf, d, mode, slice_cols, A, an,
+                       Dm, X, kind, weighted, S, d_scale, part);
+}
+
+extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale,
+                             int32_t d, const float* X, int32_t kind, float s0, float s1, float s2, int32_t slices,
+                             double* loss, float* grad, double* row_loss, void* work, void* stream) {
+  const bool source_ok = (A != nullptr) != (Dm != nullptr) && (!A || (nf >= 1 && (mode == 0 || mode == 1)));
+  if (!pair_loss_args_ok(n, d, slices) || !source_ok || !pair_loss_kind_ok(kind) || !(d_scale > 0.0f) ||
+      !isfinite(d_scale) || !X || !loss || !grad || !row_loss || !work) {
+    mde_set_error("mde_pair_loss: invalid arguments (2 <= n < 2^31, 1 <= d <= %d, exactly one of A (nf >= 1, mode 0 / "
+                  "1) and Dm, kind one of the MDE_F_L_* losses, d_scale positive and finite, 0 <= slices <= %d, "
+                  "non-null X / outputs / work)", PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+    return MDE_E_INVALID;
+  }
+  const int64_t s = cross_resolve_slices(n, n, slices);
+  if (s < 0) return (int)s;
+  hipStream_t st = mde_stream(stream);
+  double* part = static_cast<double*>(work);
+  float* an = reinterpret_cast<float*>(part + s * n * (1 + d));
+  if (A) {
+    const int rc = mde_row_sqnorm(n, nf, A, an, stream);
+    if (rc != MDE_OK) return rc;
+  }
+  const int64_t tiles = (n + KNN_BN - 1) / KNN_BN;
+  const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;     // whole tiles; the last slices may be short or empty
+  const dim3 grid((unsigned)((n + KNN_BM - 1) / KNN_BM), (unsigned)s);
+  const MdeScalars S = {s0, s1, s2};
+  const bool matrix = Dm != nullptr;
+  if (d == 1)
+    pair_loss_launch<1>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S, d_scale, part);
+  else if (d == 2)
+    pair_loss_launch<2>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S, d_scale, part);
+  else if (d == 3)
+    pair_loss_launch<3>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S, d_scale, part);
+  else
+    pair_loss_launch<PAIR_LOSS_MAX_D>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S,
+                                      d_scale, part);
+  MDE_LAUNCH_CHECK();
+  const double pairs = 0.5 * (double)n * (double)(n - 1);
+  hipLaunchKernelGGL(k_pair_loss_fold, dim3(mde_grid(n * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, (int)d,
+                     (int)s, pairs, part, row_loss, grad);
+  MDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pair_loss_total, dim3(1), dim3(MDE_BLOCK), 0, st, n, pairs, row_loss, loss);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
+}

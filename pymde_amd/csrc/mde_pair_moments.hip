@@ -22,17 +22,11 @@
 //                         same counts.
 //   k_pair_fold           adds the per-slice row sums in slice order (maxima: the largest)
 //   k_pair_totals         one workgroup reduces the rows to totals[8] in a fixed order
-#include "mde_knn_tile.h"
-#include "mde_knn_slices.h"
+#include "mde_pair.h"
 
-#define PAIR_FLT_MAX 3.402823466e+38f
-#define PAIR_COLS (KNN_BN / 4)                 // columns of a tile row that one thread walks
-#define PAIR_TILE (KNN_BM * (KNN_BN + 1))      // floats of a parked tile
 #define PAIR_MAX_BINS 64
 // A workgroup's uint32 bin counts 64 pairs per corpus column: a slice holds at most this many column tiles
 #define PAIR_HIST_MAX_TILES ((int64_t)1 << 19)
-
-__device__ __forceinline__ float pair_dist(float d2, int mode) { return mode ? 0.5f * d2 : sqrtf(d2); }
 
 template <bool HIST>
 __global__ __launch_bounds__(MDE_BLOCK) void k_pair_walk(int n, int n_q, int nfa, int nfb, int mode_a, int mode_b,
@@ -210,11 +204,6 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_totals(int64_t n_q, double p
     totals[v] = a;
   }
   if (threadIdx.x == 7) totals[7] = pairs;
-}
-
-static bool pair_args_ok(int64_t n, int64_t n_q, int32_t slices) {
-  return n >= 2 && n < ((int64_t)1 << 31) && n_q >= 1 && n_q < ((int64_t)1 << 31) && slices >= 0 &&
-         slices <= CROSS_MAX_SLICES;
 }
 
 // work: [s, n_q, 5] doubles (s > 1) | the row norms of A and B, [n] floats each | [s, n_q, 2] floats (s > 1)

@@ -13,10 +13,12 @@ import torch
 
 from pymde_amd import _lib
 from pymde_amd import constraints
+from pymde_amd import dense as _dense
 from pymde_amd import graph as _graph
 from pymde_amd import metrics as _metrics
 from pymde_amd import preprocess
 from pymde_amd import problem
+from pymde_amd import quality
 from pymde_amd import util
 from pymde_amd import quadratic
 from pymde_amd import sparse as _sparse
@@ -133,7 +135,7 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
-                       max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean"):
+                       max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False):
     """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
@@ -141,7 +143,17 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     sparse or a torch sparse COO / CSR tensor -- a data matrix, not an adjacency matrix), or a
     ``Graph``.  ``metric`` (data matrices only) as for ``distances``: the deviations are in the metric's
     own units, and ``Standardized()`` rescales them as it does Euclidean ones.  Call ``.embed()`` on the
-    result."""
+    result.
+
+    ``dense=True`` returns a ``DenseMDE`` over EVERY pair instead: no edge list, the distances are formed on
+    the fly in each evaluation (``pymde_amd.dense``).  ``max_distances`` and ``seed`` are not consulted: nothing
+    is sampled.  Data matrices under ``"euclidean"``, ``"cosine"`` or ``"correlation"`` only: a ``Graph`` or
+    ``metric="manhattan"`` is a ``ValueError``.  ``Standardized()`` rescales the deviations as above, with
+    their rms over all pairs from one ``quality.pair_moments`` pass.  With ``Anchored`` no pair is removed:
+    the anchor-anchor pairs add a constant to the value of the problem and nothing to the gradient of the free
+    rows."""
+    if dense:
+        return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric)
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
     if is_graph:
@@ -170,6 +182,28 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     return problem.MDE(n_items=n_items, embedding_dim=embedding_dim, edges=edges,
                        distortion_function=loss(deviations), constraint=constraint,
                        device=edges.device)
+
+
+def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric):
+    """``preserve_distances(dense=True)``: the ``DenseMDE`` over every pair of the rows of ``data``."""
+    metric = _dense.check_source(data, metric)
+    if not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
+        raise ValueError("`data` must be a np.ndarray/torch.Tensor/sparse data matrix for a dense problem.")
+    n_items = int(data.shape[0])
+    _dense.loss_spec(loss)
+    deviation_scale = 1.0
+    if isinstance(constraint, constraints._Standardized):
+        if device is None:
+            device = data.device if isinstance(data, torch.Tensor) and data.is_cuda else util.get_default_device()
+        device = util.require_cuda_device(device)
+        if verbose:
+            problem.LOGGER.info(f"Computing the rms of all {n_items * (n_items - 1) // 2} distances")
+        # (the embedding side of the pass is not used: one column of zeros)
+        moments = quality.pair_moments(data, torch.zeros((n_items, 1), device=device), metric=metric)
+        rms = (moments.sum_dd / moments.count) ** 0.5
+        deviation_scale = float(constraint.natural_length(n_items, embedding_dim)) / rms
+    return _dense.DenseMDE(data, embedding_dim=embedding_dim, loss=loss, constraint=constraint, metric=metric,
+                           deviation_scale=deviation_scale, device=device)
 
 
 def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p,
