@@ -395,6 +395,31 @@ int64_t mde_pair_loss_work_bytes(int64_t n, int32_t d, int32_t slices);
 int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale, int32_t d,
                   const float* X, int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
                   float* grad, double* row_loss, void* work, void* stream);
+/* The rectangular form of mde_pair_loss, what pymde_amd.DensePlacement minimises: the loss of
+ * every (query row i, corpus row j) pair, P = n_q n_c of them, with the corpus rows held fixed.
+ * XQ [n_q, d] are the free rows and XC [n_c, d] the fixed rows of the embedding (1 <= d <= 8).  D(i, j) comes from
+ * exactly one of two sources:
+ *   Q [n_q, nf] and C [n_c, nf]   the prepared data rows, both given: D = d_scale * dist(q_i, c_j) through the Gram
+ *               tile of Q against C (mode as in mde_pair_loss), the squared distance mde_knn_cross reports;
+ *   Dm [n_q, n_c]   a row-major float32 matrix of deviations with row stride n_c, Q and C NULL: nf and mode are
+ *               ignored, an entry equal to FLT_MAX is skipped, nothing else is checked.
+ * Nothing is "self": a query identical to a corpus row in both spaces is an ordinary pair with D = E = 0, which adds
+ * l(0, 0) to the loss and nothing to the gradient.  With E, l and l'(E) / E exactly as in mde_pair_loss:
+ *   row_loss double [n_q]  = sum_j l(E_ij, D_ij)
+ *   grad float [n_q, d]    = (1 / P) sum_j (l'(E_ij) / E_ij) (xq_i - xc_j)     (no gradient is formed for XC)
+ *   loss double [1]        = sum_i row_loss[i] / P                             (every pair is in one row)
+ * the average distortion of the edge-list problem over the bipartite pairs and the rows of its gradient that belong
+ * to the query rows.  The grid is (ceil(n_q / 64), slices), slices as in mde_knn_cross (0: automatic).  Sums in
+ * double, a fixed order, no floating-point atomics: for a given slice count the outputs are the same bits on every
+ * run.  With Q = C and XQ = XC the row losses are those of mde_pair_loss plus the diagonal's l(0, 0).
+ * work: mde_pair_loss_cross_work_bytes(n_q, n_c, d, slices) = s n_q (1 + d) 8 + 4 (n_q + n_c) bytes (the per-slice
+ * partials, the row norms of Q and of C); the call allocates nothing.  1 <= n_q, n_c < 2^31.  Arguments are checked
+ * on the host before any launch: MDE_E_INVALID with a message.  ASYNC. */
+int64_t mde_pair_loss_cross_work_bytes(int64_t n_q, int64_t n_c, int32_t d, int32_t slices);
+int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                        const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC, int32_t kind,
+                        float s0, float s1, float s2, int32_t slices, double* loss, float* grad, double* row_loss,
+                        void* work, void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

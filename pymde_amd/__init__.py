@@ -9,6 +9,8 @@ __version__ = "0.1.0"
 
 from pymde_amd.problem import MDE  # noqa: F401
 from pymde_amd.dense import DenseMDE  # noqa: F401
+from pymde_amd.dense import DensePlacement  # noqa: F401
+from pymde_amd.dense import LandmarkMDE  # noqa: F401
 from pymde_amd.constraints import Centered, Anchored, Standardized  # noqa: F401
 from pymde_amd.functions import losses, penalties  # noqa: F401
 from pymde_amd.util import align, all_edges, center, rotate, seed  # noqa: F401

@@ -96,6 +96,9 @@ SYMBOLS = {
     "mde_pair_loss_work_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "mde_pair_loss": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_i32,
                               c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_pair_loss_cross_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "mde_pair_loss_cross": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp, c_i32,
+                                    c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_ann_search": (c_i32, [c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
                                c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_ann_centroids": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),

@@ -24,6 +24,12 @@
 //   k_pair_loss_fold   adds the per-slice partials in slice order: row_loss, and grad = G / P rounded once
 //   k_pair_loss_total  one workgroup reduces row_loss to the loss in a fixed order
 // For a given slice count the loss, the gradient and row_loss are the same bits on every run.
+//
+// mde_pair_loss_cross is the RECTANGULAR form, what pymde_amd.DensePlacement minimises: the rows
+// are n_q free query rows (Q, XQ), the columns n_c fixed corpus rows (C, XC), D comes from the Gram tile of Q against
+// C or from an [n_q, n_c] matrix, and nothing is "self".  The same kernels: k_pair_loss_walk takes the rows and the
+// columns from two sets of pointers and drops the row != col test at compile time (SELF = false); the fold divides
+// by P = n_q n_c and the total by 1 P instead of 2 P, since every pair is in one row.  No gradient for XC.
 #include <math.h>
 
 #include "mde_pair.h"
@@ -32,12 +38,15 @@
 #define PAIR_LOSS_MAX_D 8
 #define PAIR_LOSS_XS (KNN_BN * PAIR_LOSS_MAX_D)   // floats of the staged column rows of X: 2 KB
 
-template <int DC, bool MATRIX>
-__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n, int nf, int d, int mode, int64_t slice_cols,
-                                                              const float* __restrict__ A,
-                                                              const float* __restrict__ an,
+template <int DC, bool MATRIX, bool SELF>
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, int nf, int d, int mode,
+                                                              int64_t slice_cols, const float* __restrict__ Q,
+                                                              const float* __restrict__ qn,
+                                                              const float* __restrict__ C,
+                                                              const float* __restrict__ cn,
                                                               const float* __restrict__ Dm,
-                                                              const float* __restrict__ X, int kind, int weighted,
+                                                              const float* __restrict__ XQ,
+                                                              const float* __restrict__ XC, int kind, int weighted,
                                                               MdeScalars S, float d_scale,
                                                               double* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -46,35 +55,38 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n, int nf, int
   const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
   const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
   const int64_t lo = (int64_t)blockIdx.y * slice_cols;
-  const int64_t c_lo = lo < n ? lo : n, c_hi = lo + slice_cols < n ? lo + slice_cols : n;
+  const int64_t c_lo = lo < n_c ? lo : n_c, c_hi = lo + slice_cols < n_c ? lo + slice_cols : n_c;
   float xi[DC];                                                 // the thread's own row
 #pragma unroll
-  for (int k = 0; k < DC; ++k) xi[k] = (row0 + r < n && k < d) ? X[(row0 + r) * d + k] : 0.0f;
+  for (int k = 0; k < DC; ++k) xi[k] = (row0 + r < n_q && k < d) ? XQ[(row0 + r) * d + k] : 0.0f;
   const float* arow[KNN_STG];
   bool qok[KNN_STG];
   if constexpr (!MATRIX) {
 #pragma unroll
     for (int q = 0; q < KNN_STG; ++q) {
       const int64_t gr = row0 + (tid >> 5) + 8 * q;
-      qok[q] = gr < n;
-      arow[q] = A + (qok[q] ? gr : 0) * nf;
+      qok[q] = gr < n_q;
+      arow[q] = Q + (qok[q] ? gr : 0) * nf;
     }
   }
   double sl = 0.0, sg[DC];
 #pragma unroll
   for (int k = 0; k < DC; ++k) sg[k] = 0.0;
   for (int64_t col0 = c_lo; col0 < c_hi; col0 += KNN_BN) {
-    auto keep = [&](int rr, int cc) { return row0 + rr < n && col0 + cc < n && row0 + rr != col0 + cc; };
+    auto keep = [&](int rr, int cc) {
+      return row0 + rr < n_q && col0 + cc < n_c && (!SELF || row0 + rr != col0 + cc);
+    };
     if constexpr (MATRIX) {
       // wave w takes the tile rows w, w + 4, ...: all sixteen loads go out from clamped addresses before the first is
-      // used, and what the tile does not have (or the diagonal) is replaced when the registers are parked
+      // used, and what the tile does not have (or the diagonal of the square walk) is replaced when the registers are
+      // parked
       const int lane = tid & 63;
-      const int64_t gc = col0 + lane < n ? col0 + lane : n - 1;
+      const int64_t gc = col0 + lane < n_c ? col0 + lane : n_c - 1;
       float v[KNN_BM / 4];
 #pragma unroll
       for (int q = 0; q < KNN_BM / 4; ++q) {
-        const int64_t gr = row0 + w + 4 * q < n ? row0 + w + 4 * q : n - 1;
-        v[q] = Dm[gr * (int64_t)n + gc];
+        const int64_t gr = row0 + w + 4 * q < n_q ? row0 + w + 4 * q : n_q - 1;
+        v[q] = Dm[gr * (int64_t)n_c + gc];
       }
       __syncthreads();                                          // the walk of the last tile is over
 #pragma unroll
@@ -86,16 +98,16 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n, int nf, int
 #pragma unroll
       for (int q = 0; q < KNN_STG; ++q) {
         const int64_t gc = col0 + (tid >> 5) + 8 * q;
-        cok[q] = gc < n;
-        acol[q] = A + (cok[q] ? gc : n - 1) * nf;
+        cok[q] = gc < n_c;
+        acol[q] = C + (cok[q] ? gc : n_c - 1) * nf;
       }
       // the park follows the barriers of knn_gram_tile: every thread is past the walk of the last tile by then
       const f32x16 acc = knn_gram_tile(s.sA, s.sB, nf, arow, qok, acol, cok);
-      knn_park_tile(s.sD, acc, keep, [&](int rr) { return an[row0 + rr]; }, [&](int cc) { return an[col0 + cc]; });
+      knn_park_tile(s.sD, acc, keep, [&](int rr) { return qn[row0 + rr]; }, [&](int cc) { return cn[col0 + cc]; });
     }
     for (int i = tid; i < KNN_BN * DC; i += MDE_BLOCK) {
       const int c = i / DC, k = i - c * DC;
-      sX[i] = (col0 + c < n && k < d) ? X[(col0 + c) * d + k] : 0.0f;
+      sX[i] = (col0 + c < n_c && k < d) ? XC[(col0 + c) * d + k] : 0.0f;
     }
     __syncthreads();
     const float* pd = s.sD + r * (KNN_BN + 1) + w * PAIR_COLS;
@@ -132,18 +144,19 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n, int nf, int
   // thread (row, v) adds value v of the row's four threads in thread order
   for (int i = tid; i < KNN_BM * NV; i += MDE_BLOCK) {
     const int rr = i / NV, v = i - NV * rr;
-    if (row0 + rr < n && v <= d) {
+    if (row0 + rr < n_q && v <= d) {
       double t = cs[((size_t)0 * KNN_BM + rr) * NV + v];
 #pragma unroll
       for (int u = 1; u < 4; ++u) t += cs[((size_t)u * KNN_BM + rr) * NV + v];
-      part[((int64_t)blockIdx.y * n + row0 + rr) * (1 + d) + v] = t;
+      part[((int64_t)blockIdx.y * n_q + row0 + rr) * (1 + d) + v] = t;
     }
   }
 }
 static_assert(4 * KNN_BM * (1 + PAIR_LOSS_MAX_D) * sizeof(double) <= 2 * PAIR_TILE * sizeof(float),
               "the row partials must fit in the parked tile and the tile after it");
 
-// row_loss[i] and grad[i, :] = G[i, :] / P from the per-slice partials [slices, n, 1 + d], added in slice order.
+// row_loss[i] and grad[i, :] = G[i, :] / pairs from the per-slice partials [slices, n, 1 + d], added in slice order
+// (n rows: the rows of the square problem, the query rows of the rectangular one).
 __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold(int64_t n, int d, int slices, double pairs,
                                                               const double* __restrict__ part,
                                                               double* __restrict__ row_loss,
@@ -162,8 +175,9 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold(int64_t n, int d, 
 }
 
 // One workgroup: thread t adds the rows t, t + 256, ... in row order, thread 0 then adds the 256 threads' sums in
-// thread order.  loss = sum_i row_loss[i] / (2 P): every pair is in two rows.
-__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_total(int64_t n, double pairs,
+// thread order.  loss = sum_i row_loss[i] / (factor * pairs): factor 2 for the square problem, where every pair is in
+// two rows, 1 for the rectangular one.
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_total(int64_t n, double pairs, double factor,
                                                                const double* __restrict__ row_loss,
                                                                double* __restrict__ loss) {
   __shared__ double sums[MDE_BLOCK];
@@ -174,13 +188,17 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_total(int64_t n, double
   if (threadIdx.x == 0) {
     double a = sums[0];
     for (int u = 1; u < MDE_BLOCK; ++u) a += sums[u];
-    loss[0] = a / (2.0 * pairs);
+    loss[0] = a / (factor * pairs);
   }
 }
 
 static bool pair_loss_kind_ok(int32_t kind) { return kind >= MDE_F_L_QUADRATIC && kind <= MDE_F_L_LOG1P; }
 static bool pair_loss_args_ok(int64_t n, int32_t d, int32_t slices) {
   return pair_args_ok(n, n, slices) && d >= 1 && d <= PAIR_LOSS_MAX_D;
+}
+static bool pair_loss_cross_args_ok(int64_t n_q, int64_t n_c, int32_t d, int32_t slices) {
+  return n_q >= 1 && n_q < ((int64_t)1 << 31) && n_c >= 1 && n_c < ((int64_t)1 << 31) && slices >= 0 &&
+         slices <= CROSS_MAX_SLICES && d >= 1 && d <= PAIR_LOSS_MAX_D;
 }
 
 // work: [s, n, 1 + d] doubles | the row norms of A, [n] floats (the Gram source; the room is there for either source)
@@ -195,18 +213,64 @@ extern "C" int64_t mde_pair_loss_work_bytes(int64_t n, int32_t d, int32_t slices
   return s * n * (1 + d) * 8 + 4 * n;
 }
 
-template <int DC>
-static void pair_loss_launch(bool matrix, dim3 grid, hipStream_t st, int n, int nf, int d, int mode, int64_t slice_cols,
-                             const float* A, const float* an, const float* Dm, const float* X, int kind,
-                             MdeScalars S, float d_scale, double* part) {
+// work: [s, n_q, 1 + d] doubles | the row norms of Q, [n_q] floats | the row norms of C, [n_c] floats
+extern "C" int64_t mde_pair_loss_cross_work_bytes(int64_t n_q, int64_t n_c, int32_t d, int32_t slices) {
+  if (!pair_loss_cross_args_ok(n_q, n_c, d, slices)) {
+    mde_set_error("mde_pair_loss_cross_work_bytes: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, 0 <= slices "
+                  "<= %d)", PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+    return MDE_E_INVALID;
+  }
+  const int64_t s = cross_resolve_slices(n_q, n_c, slices);
+  if (s < 0) return s;
+  return s * n_q * (1 + d) * 8 + 4 * (n_q + n_c);
+}
+
+template <int DC, bool SELF>
+static void pair_loss_launch_dc(bool matrix, dim3 grid, hipStream_t st, int n_q, int n_c, int nf, int d, int mode,
+                                int64_t slice_cols, const float* Q, const float* qn, const float* C, const float* cn,
+                                const float* Dm, const float* XQ, const float* XC, int kind, MdeScalars S,
+                                float d_scale, double* part) {
   const size_t lds = knn_tile_lds_bytes(0, PAIR_TILE + PAIR_LOSS_XS);
   const int weighted = kind == MDE_F_L_WEIGHTED_QUADRATIC || kind == MDE_F_L_WEIGHTED_POWER;
   if (matrix)
-    hipLaunchKernelGGL((k_pair_loss_walk<DC, true>), grid, dim3(MDE_BLOCK), lds, st, n, nf, d, mode, slice_cols, A, an,
-                       Dm, X, kind, weighted, S, d_scale, part);
+    hipLaunchKernelGGL((k_pair_loss_walk<DC, true, SELF>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf, d, mode,
+                       slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part);
   else
-    hipLaunchKernelGGL((k_pair_loss_walk<DC, false>), grid, dim3(MDE_BLOCK), lds, st, n, nf, d, mode, slice_cols, A, an,
-                       Dm, X, kind, weighted, S, d_scale, part);
+    hipLaunchKernelGGL((k_pair_loss_walk<DC, false, SELF>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf, d, mode,
+                       slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part);
+}
+
+// The walk, the fold and the total of either problem on checked arguments: SELF is the square problem (rows and
+// columns are the same items, the diagonal is left out, every pair is in two rows), !SELF the rectangular one.
+// part [s, n_q, 1 + d]; qn / cn are read by the Gram source only.
+template <bool SELF>
+static int pair_loss_run(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* qn, const float* C,
+                         const float* cn, int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                         const float* XC, int32_t kind, MdeScalars S, int64_t s, double pairs, double* loss,
+                         float* grad, double* row_loss, double* part, hipStream_t st) {
+  const int64_t tiles = (n_c + KNN_BN - 1) / KNN_BN;
+  const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;     // whole tiles; the last slices may be short or empty
+  const dim3 grid((unsigned)((n_q + KNN_BM - 1) / KNN_BM), (unsigned)s);
+  const bool matrix = Dm != nullptr;
+  if (d == 1)
+    pair_loss_launch_dc<1, SELF>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C, cn, Dm, XQ,
+                                 XC, kind, S, d_scale, part);
+  else if (d == 2)
+    pair_loss_launch_dc<2, SELF>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C, cn, Dm, XQ,
+                                 XC, kind, S, d_scale, part);
+  else if (d == 3)
+    pair_loss_launch_dc<3, SELF>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C, cn, Dm, XQ,
+                                 XC, kind, S, d_scale, part);
+  else
+    pair_loss_launch_dc<PAIR_LOSS_MAX_D, SELF>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
+                                               cn, Dm, XQ, XC, kind, S, d_scale, part);
+  MDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pair_loss_fold, dim3(mde_grid(n_q * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_q,
+                     (int)d, (int)s, pairs, part, row_loss, grad);
+  MDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pair_loss_total, dim3(1), dim3(MDE_BLOCK), 0, st, n_q, pairs, SELF ? 2.0 : 1.0, row_loss, loss);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
 }
 
 extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale,
@@ -222,33 +286,45 @@ extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode
   }
   const int64_t s = cross_resolve_slices(n, n, slices);
   if (s < 0) return (int)s;
-  hipStream_t st = mde_stream(stream);
   double* part = static_cast<double*>(work);
   float* an = reinterpret_cast<float*>(part + s * n * (1 + d));
   if (A) {
     const int rc = mde_row_sqnorm(n, nf, A, an, stream);
     if (rc != MDE_OK) return rc;
   }
-  const int64_t tiles = (n + KNN_BN - 1) / KNN_BN;
-  const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;     // whole tiles; the last slices may be short or empty
-  const dim3 grid((unsigned)((n + KNN_BM - 1) / KNN_BM), (unsigned)s);
   const MdeScalars S = {s0, s1, s2};
-  const bool matrix = Dm != nullptr;
-  if (d == 1)
-    pair_loss_launch<1>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S, d_scale, part);
-  else if (d == 2)
-    pair_loss_launch<2>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S, d_scale, part);
-  else if (d == 3)
-    pair_loss_launch<3>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S, d_scale, part);
-  else
-    pair_loss_launch<PAIR_LOSS_MAX_D>(matrix, grid, st, (int)n, nf, d, mode, slice_cols, A, an, Dm, X, kind, S,
-                                      d_scale, part);
-  MDE_LAUNCH_CHECK();
   const double pairs = 0.5 * (double)n * (double)(n - 1);
-  hipLaunchKernelGGL(k_pair_loss_fold, dim3(mde_grid(n * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, (int)d,
-                     (int)s, pairs, part, row_loss, grad);
-  MDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_pair_loss_total, dim3(1), dim3(MDE_BLOCK), 0, st, n, pairs, row_loss, loss);
-  MDE_LAUNCH_CHECK();
-  return MDE_OK;
+  return pair_loss_run<true>(n, n, nf, A, an, A, an, mode, Dm, d_scale, d, X, X, kind, S, s, pairs, loss, grad,
+                             row_loss, part, mde_stream(stream));
+}
+
+// The rectangular problem: every (query row, corpus row) pair, a gradient for the query rows only.
+extern "C" int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                                   const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
+                                   int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
+                                   float* grad, double* row_loss, void* work, void* stream) {
+  const bool gram = Q != nullptr && C != nullptr && Dm == nullptr;
+  const bool matrix = Q == nullptr && C == nullptr && Dm != nullptr;
+  const bool source_ok = matrix || (gram && nf >= 1 && (mode == 0 || mode == 1));
+  if (!pair_loss_cross_args_ok(n_q, n_c, d, slices) || !source_ok || !pair_loss_kind_ok(kind) || !(d_scale > 0.0f) ||
+      !isfinite(d_scale) || !XQ || !XC || !loss || !grad || !row_loss || !work) {
+    mde_set_error("mde_pair_loss_cross: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and C (nf "
+                  ">= 1, mode 0 / 1) or Dm alone, kind one of the MDE_F_L_* losses, d_scale positive and finite, 0 <= "
+                  "slices <= %d, non-null XQ / XC / outputs / work)", PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+    return MDE_E_INVALID;
+  }
+  const int64_t s = cross_resolve_slices(n_q, n_c, slices);
+  if (s < 0) return (int)s;
+  double* part = static_cast<double*>(work);
+  float* qn = reinterpret_cast<float*>(part + s * n_q * (1 + d));
+  float* cn = qn + n_q;
+  if (gram) {
+    int rc = mde_row_sqnorm(n_q, nf, Q, qn, stream);
+    if (rc == MDE_OK) rc = mde_row_sqnorm(n_c, nf, C, cn, stream);
+    if (rc != MDE_OK) return rc;
+  }
+  const MdeScalars S = {s0, s1, s2};
+  const double pairs = (double)n_q * (double)n_c;
+  return pair_loss_run<false>(n_q, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s, pairs, loss, grad,
+                              row_loss, part, mde_stream(stream));
 }

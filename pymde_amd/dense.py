@@ -10,6 +10,11 @@ data matrix -- every evaluation forms the distances on the fly with the Gram til
 
 The solver is the one ``MDE.embed`` calls (``optim.lbfgs``), on its generic path: the objective is a
 ``torch.autograd.Function`` around ``mde_pair_loss``, the constraint any ``Constraint``.
+
+``DensePlacement`` is the rectangular form (``mde_pair_loss_cross``): the loss of every (new row,
+embedded row) pair with the embedded rows held fixed, which places new rows into a finished distance-preserving
+embedding.  ``LandmarkMDE`` (``preserve_distances(landmarks=m)``) is landmark MDS on the two: a ``DenseMDE`` of m
+landmark rows, then a ``DensePlacement`` of all the others against them.
 """
 import collections
 import math
@@ -303,4 +308,327 @@ class DenseMDE(object):
             if solve_stats.iterations > 0:
                 _problem.LOGGER.info(f"average distortion {self.value:.3g} | "
                                      f"residual norm {self.residual_norm:.1e}")
+        return self.X
+
+
+# ---------------------------------------------------------------------- the rectangular problem
+def _pair_loss_cross(XQ, XC, spec, Q=None, C=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=None):
+    """``mde_pair_loss_cross`` on prepared float32 tensors on one GPU: ``(loss float64 [1], grad float32 [n_q, d],
+    row_loss float64 [n_q])`` on that GPU.  Either both ``Q`` and ``C`` (the prepared data rows of the free and of
+    the fixed items) or ``Dm`` (the [n_q, n_c] matrix)."""
+    n_q, n_c, d, device = int(XQ.shape[0]), int(XC.shape[0]), int(XQ.shape[1]), XQ.device
+    lib = _lib.load()
+    loss = torch.empty(1, dtype=torch.float64, device=device)
+    grad = torch.empty((n_q, d), dtype=torch.float32, device=device)
+    row_loss = torch.empty(n_q, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        if work is None:
+            work = _work_cross(lib, n_q, n_c, d, slices, device)
+        _lib.check(lib.mde_pair_loss_cross(n_q, n_c, 0 if Q is None else int(Q.shape[1]), _lib.ptr(Q), _lib.ptr(C),
+                                           mode, _lib.ptr(Dm), float(d_scale), d, _lib.ptr(XQ), _lib.ptr(XC),
+                                           spec.kind, spec.scalars[0], spec.scalars[1], spec.scalars[2], slices,
+                                           _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(row_loss), _lib.ptr(work),
+                                           _lib.stream_ptr(device)))
+    return loss, grad, row_loss
+
+
+def _work_cross(lib, n_q, n_c, d, slices, device):
+    nbytes = int(lib.mde_pair_loss_cross_work_bytes(n_q, n_c, d, slices))
+    if nbytes < 0:
+        _lib.check(nbytes)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _check_rectangular_matrix(D):
+    """Finite and non-negative (a rectangular matrix has no symmetry to check): one pass on the GPU in row blocks,
+    one read-back; ``ValueError`` saying which."""
+    rows, cols = int(D.shape[0]), int(D.shape[1])
+    flags = torch.zeros(2, dtype=torch.int64, device=D.device)
+    step = max(1, min(rows, (1 << 24) // cols))
+    for lo in range(0, rows, step):
+        block = D[lo:lo + step]
+        flags[0] += (~torch.isfinite(block)).sum()
+        flags[1] += (block < 0).sum()
+    bad, negative = flags.tolist()
+    if bad:
+        raise ValueError(f"`distance_matrix` is not finite: {bad} of its entries are NaN or infinite")
+    if negative:
+        raise ValueError(f"`distance_matrix` is not non-negative: {negative} of its entries are below zero")
+
+
+class _Free(constraints.Constraint):
+    """The constraint of a placement: none.  The new rows are free and the fixed rows are not variables of the
+    solve, so there is nothing to project onto, not even the centring of ``Centered``."""
+
+    def name(self):
+        return "free"
+
+    def initialization(self, n_items, embedding_dim, device=None):
+        return constraints._randn(n_items, embedding_dim, device)
+
+    def project_onto_constraint(self, Z, inplace=True):
+        return Z if inplace else Z.detach().clone()
+
+    def project_onto_tangent_space(self, X, Z, inplace=True):
+        del X
+        return Z if inplace else Z.detach().clone()
+
+
+class DensePlacement(DenseMDE):
+    """Out-of-sample placement into a distance-preserving embedding: minimise, over the ``n_new`` new rows alone, the
+    mean over all ``p = n_new * n_old`` (new row, embedded row) pairs of ``loss(|x_new - x_old|, D)``, with the
+    embedded rows held where they are -- the rectangular form of ``DenseMDE`` (``mde_pair_loss_cross``, DESIGN section
+    6k).  No new-new pair and no old-old pair takes part; a second ``DenseMDE`` over old + new rows with ``Anchored``
+    would walk ``(n_old + n_new)^2`` pairs and include both.
+
+    Exactly one source of the deviations ``D``:
+
+    ``data`` [n_old, n_features] and ``new_data`` [n_new, n_features]: dense or sparse data matrices, prepared as
+    ``preprocess.cross_nearest_neighbors`` prepares its corpus and its queries (Euclidean: both minus the column
+    means of ``data`` when that offset dominates; cosine / correlation: unit rows), so ``D`` is the distance that
+    search reports, formed on the fly in every evaluation.
+    ``distance_matrix`` [n_new, n_old] (with ``data=None, new_data=None``): rectangular, new against old, kept as
+    float32 on the GPU and checked once to be finite and non-negative.
+
+    ``X`` [n_old, d] is the embedding of the old rows; it is used as float32 and never modified, and ``d`` (1 .. 8)
+    is taken from it.  ``loss`` and ``deviation_scale`` as for ``DenseMDE``.  A new row identical to an old one in
+    both spaces is an ordinary pair (D = E = 0).
+
+    ``embed()`` starts, by default, every new row at the mean of the embedding vectors of its ``d + 1`` nearest old
+    rows (``d + 1`` points fix a position in R^d; perturbed by 1e-4 if a new row lands exactly on an old one), and
+    runs ONE L-BFGS over all new rows, although the objective is separable over them.  After it: ``X`` (the new
+    rows, [n_new, d]), ``solve_stats``, ``value`` and ``residual_norm``; ``embedding()`` is ``cat([X_old, X_new])``."""
+
+    def __init__(self, data, X, new_data, loss=losses.Absolute, metric="euclidean", deviation_scale=1.0,
+                 distance_matrix=None, device=None):
+        from_data = data is not None or new_data is not None
+        if from_data == (distance_matrix is not None):
+            raise ValueError("exactly one source of the deviations must be given: `data` and `new_data`, or "
+                             "`distance_matrix` [n_new, n_old] with data=None and new_data=None")
+        if from_data and (data is None or new_data is None):
+            raise ValueError("`data` (the embedded rows) and `new_data` (the rows to place) must be given together")
+        if not hasattr(X, "shape") or len(X.shape) != 2:
+            raise ValueError("`X` must be the embedding [n_old, d] of the embedded rows, got shape "
+                             f"{tuple(getattr(X, 'shape', ()))}")
+        n_old, embedding_dim = int(X.shape[0]), int(X.shape[1])
+        if not 1 <= embedding_dim <= MAX_DIM:
+            raise ValueError(f"the embedding dimension (the columns of `X`) must lie in [1, {MAX_DIM}] for a dense "
+                             f"problem, got {embedding_dim}")
+        self._spec = loss_spec(loss)
+        deviation_scale = float(deviation_scale)
+        if not (deviation_scale > 0.0 and math.isfinite(deviation_scale)):
+            raise ValueError(f"deviation_scale must be a positive finite number, got {deviation_scale!r}")
+        if from_data:
+            for m in (data, new_data):
+                metric = check_source(m, metric)
+            quality._check_matrix(data, "data")
+            quality._check_matrix(new_data, "new_data")
+            if int(data.shape[0]) != n_old:
+                raise ValueError(f"`X` must hold one embedding vector per row of `data` ({int(data.shape[0])}); got "
+                                 f"shape {tuple(X.shape)}")
+            if int(new_data.shape[1]) != int(data.shape[1]):
+                raise ValueError(f"`new_data` has {int(new_data.shape[1])} features and `data` has "
+                                 f"{int(data.shape[1])}; they must agree")
+            n_new = int(new_data.shape[0])
+        else:
+            shape = tuple(getattr(distance_matrix, "shape", ()))
+            if len(shape) != 2 or int(shape[1]) != n_old:
+                raise ValueError(f"`distance_matrix` must be rectangular [n_new, n_old = {n_old}], new rows against "
+                                 f"the rows of `X`; got shape {shape}")
+            n_new = int(shape[0])
+        if n_old < 1:
+            raise ValueError("a placement needs at least one embedded row")
+        if n_new < 1:
+            raise ValueError("`new_data` needs at least one row" if from_data else
+                             "`distance_matrix` needs at least one row")
+        if device is None:
+            on_gpu = [t.device for t in (X, data, new_data, distance_matrix)
+                      if isinstance(t, torch.Tensor) and t.is_cuda]
+            device = on_gpu[0] if on_gpu else util.get_default_device()
+        self.device = util.require_cuda_device(device)
+        # (a copy: the caller's tensor is neither written nor followed)
+        self._X_old = torch.as_tensor(X).detach().to(device=self.device, dtype=torch.float32, copy=True).contiguous()
+        if not bool(torch.isfinite(self._X_old).all()):
+            raise ValueError("`X` holds NaN or infinite entries")
+        self._A, self._Q, self._Dm, self._mode = None, None, None, 0
+        if from_data:
+            Q = preprocess._dense_rows_for_cross(new_data, self.device, "new_data")
+            C = preprocess._dense_rows_for_cross(data, self.device, "data")
+            if metric == _metrics.EUCLIDEAN:
+                _metrics.check_finite(Q, "`new_data`")
+                Q, C = preprocess._translated_pair(Q, C)
+            else:
+                Q, C = _metrics.normalized_rows(Q, metric), _metrics.normalized_rows(C, metric)
+            self._Q, self._A = Q.contiguous(), C.contiguous()
+            self._mode = quality._pair_modes(metric)[0]
+        else:
+            self._Dm = torch.as_tensor(distance_matrix).to(device=self.device, dtype=torch.float32).contiguous()
+            _check_rectangular_matrix(self._Dm)
+        self.n_items = n_new
+        self.n_old = n_old
+        self.embedding_dim = embedding_dim
+        self.p = n_new * n_old
+        self.metric = metric if from_data else None
+        self.deviation_scale = deviation_scale
+        self.loss = loss
+        self.constraint = _Free()
+        self.X = None
+        self.solve_stats = None
+        self.value = None
+        self.residual_norm = None
+        self._work_buffer = None
+
+    def __str__(self):
+        source = "data matrices, metric %s" % self.metric if self._A is not None else "distance matrix"
+        return ("Dense placement problem:\n\tn (number of new items) {0}\n\tembedded items, held fixed {1}\n"
+                "\tm (embedding dimension) {2}\n\tp (number of pairs, new against embedded) {3}\n"
+                "\tdeviations from {4}\n\tdevice {5}".format(self.n_items, self.n_old, self.embedding_dim, self.p,
+                                                              source, self.device))
+
+    def _evaluate(self, X):
+        """(loss float64 [1], grad float32 [n_new, d], row_loss float64 [n_new]) at a float32 X on the device."""
+        if self._work_buffer is None:
+            with torch.cuda.device(self.device):
+                self._work_buffer = _work_cross(_lib.load(), self.n_items, self.n_old, self.embedding_dim, 0,
+                                                self.device)
+        return _pair_loss_cross(X.contiguous(), self._X_old, self._spec, Q=self._Q, C=self._A, mode=self._mode,
+                                Dm=self._Dm, d_scale=self.deviation_scale, work=self._work_buffer)
+
+    def average_distortion(self, X=None):
+        """The average distortion of the new rows ``X`` [n_new, d] over all ``n_new * n_old`` pairs with the embedded
+        rows (a 0-dim float32 tensor; differentiable w.r.t. ``X``)."""
+        return _DenseDistortion.apply(self._embedding_arg(X), self)
+
+    def item_distortions(self, X=None):
+        """float32 [n_new]: for every new row the mean of the loss over its ``n_old`` pairs.  Their mean is the
+        average distortion."""
+        row_loss = self._evaluate(self._embedding_arg(X).detach())[2]
+        return (row_loss / float(self.n_old)).to(torch.float32)
+
+    def initialization(self):
+        """The default start [n_new, d]: every new row at the mean of the embedding vectors of its ``d + 1`` nearest
+        embedded rows (fewer when there are fewer), perturbed by 1e-4 if a new row lands exactly on one of
+        them."""
+        k = min(self.embedding_dim + 1, self.n_old)
+        if self._Dm is not None:
+            idx = torch.topk(self._Dm, k, dim=1, largest=False).indices
+        else:
+            # (the prepared rows: translating both by one vector, or normalising each, is idempotent)
+            idx = preprocess._cross_knn_lists(self._Q, self._A, k)[0].to(torch.int64)
+        X_new = self._X_old[idx].mean(1)
+        on_old = (self._X_old[idx] == X_new.unsqueeze(1)).all(2).any()
+        if bool(on_old):
+            X_new = X_new + 1e-4 * torch.randn(X_new.shape, device=self.device, dtype=X_new.dtype)
+        return X_new.contiguous()
+
+    def embed(self, X=None, eps=1e-5, max_iter=300, memory_size=10, verbose=False, print_every=None,
+              snapshot_every=None):
+        """Place the new rows; stores them in ``self.X`` [n_new, d] and returns them.  ``X``: their start (default:
+        ``initialization()``).  Other arguments as in ``MDE.embed``."""
+        if X is None:
+            X = self.initialization()
+        return super().embed(X, eps=eps, max_iter=max_iter, memory_size=memory_size, verbose=verbose,
+                             print_every=print_every, snapshot_every=snapshot_every)
+
+    def embedding(self, X=None):
+        """``cat([X_old, X_new])`` [n_old + n_new, d]: the embedded rows, bit for bit, then the placed ones."""
+        return torch.cat([self._X_old, self._embedding_arg(X).detach()])
+
+
+LandmarkSolveStats = collections.namedtuple("LandmarkSolveStats", ["landmarks", "placement"])
+LandmarkSolveStats.__doc__ = """The ``SolveStats`` of the two stages of ``LandmarkMDE.embed``."""
+
+
+def _take_rows(data, rows):
+    """The rows ``rows`` (int64, on the CPU) of a dense or sparse data matrix, in the container it came in."""
+    if isinstance(data, torch.Tensor):
+        if data.layout != torch.strided:
+            return data.to_sparse_coo().index_select(0, rows.to(data.device)).coalesce()
+        return data[rows.to(data.device)]
+    if hasattr(data, "tocsr"):
+        return data.tocsr()[rows.numpy()]
+    return data[rows.numpy()]
+
+
+def check_landmarks(landmarks, n_items, constraint):
+    """``landmarks`` as an int in ``[2, n_items)``; ``ValueError`` otherwise, and for a constraint the placed rows
+    cannot keep (no device is needed to say so)."""
+    if isinstance(landmarks, bool) or int(landmarks) != landmarks:
+        raise ValueError(f"`landmarks` must be a number of rows (an int), got {landmarks!r}")
+    landmarks = int(landmarks)
+    if not 2 <= landmarks < n_items:
+        raise ValueError(f"`landmarks` must lie in [2, n) = [2, {n_items}): the landmarks need a pair among "
+                         f"themselves and at least one row must be left to place; got {landmarks}")
+    if constraint is not None and not isinstance(constraint, constraints._Centered):
+        raise ValueError(f"landmarks take constraint=None or Centered(), not {constraint.name()}: the placed rows "
+                         "are unconstrained (each is put where its distances to the landmarks say), so the whole "
+                         "embedding would be neither standardized nor anchored")
+    return landmarks
+
+
+class LandmarkMDE(object):
+    """Landmark MDS: embed ``landmarks`` rows of ``data``, drawn uniformly without replacement, with a ``DenseMDE``
+    over all their pairs, then place every other row against them with a ``DensePlacement``.  A sweep costs
+    O(m^2 + n m) pair evaluations instead of the O(n^2) of the full dense problem, and the pairs among the placed
+    rows are never looked at.  ``preserve_distances(data, landmarks=m)`` builds it.
+
+    ``data``, ``embedding_dim``, ``loss``, ``metric`` as for ``DenseMDE``; ``constraint`` is ``None`` or
+    ``Centered()``: the result is centred, and the placed rows can keep no other constraint.  ``seed`` draws the
+    landmarks (``quality._sample_rows``): the same seed gives the same ``landmarks``.
+
+    After ``embed()``: ``X`` [n, d] in the row order of ``data``, ``landmarks`` (int64 indices), ``landmark_problem``
+    (the ``DenseMDE``), ``placement`` (the ``DensePlacement``), ``value`` (the placement's value) and ``solve_stats``
+    (a ``LandmarkSolveStats`` of both stages).  Score the result with ``quality.stress(data, X, sample=...)``."""
+
+    def __init__(self, data, landmarks, embedding_dim=2, loss=losses.Absolute, constraint=None, metric="euclidean",
+                 seed=None, device=None):
+        metric = check_source(data, metric)
+        quality._check_matrix(data, "data")
+        n = int(data.shape[0])
+        m = check_landmarks(landmarks, n, constraint)
+        embedding_dim = int(embedding_dim)
+        if not 1 <= embedding_dim <= MAX_DIM:
+            raise ValueError(f"embedding_dim must lie in [1, {MAX_DIM}] for a dense problem, got {embedding_dim}")
+        loss_spec(loss)
+        if seed is None:
+            seed = int(util.np_rng().integers(0, 2 ** 63 - 1))
+        self.n_items = n
+        self.embedding_dim = embedding_dim
+        self.metric = metric
+        self.loss = loss
+        self.landmarks = quality._sample_rows(n, m, seed).to(torch.int64)
+        placed = torch.ones(n, dtype=torch.bool)
+        placed[self.landmarks] = False
+        self.placed = placed.nonzero().reshape(-1)
+        self._data = data
+        self._landmark_data = _take_rows(data, self.landmarks)
+        self.landmark_problem = DenseMDE(self._landmark_data, embedding_dim=embedding_dim, loss=loss,
+                                         constraint=constraints.Centered(), metric=metric, device=device)
+        self.device = self.landmark_problem.device
+        self.placement = None
+        self.X = None
+        self.value = None
+        self.solve_stats = None
+
+    def embed(self, X=None, **solver_args):
+        """Embed the landmarks, place the other rows, centre the whole: stores the [n, d] embedding in ``self.X`` and
+        returns it.  ``X``: an optional [n, d] start for both stages; ``solver_args`` as in ``DenseMDE.embed``, for
+        both stages."""
+        start_l = start_p = None
+        if X is not None:
+            if tuple(X.shape) != (self.n_items, self.embedding_dim):
+                raise ValueError(f"the start must have shape ({self.n_items}, {self.embedding_dim}), got "
+                                 f"{tuple(X.shape)}")
+            X = X.detach().to(device=self.device, dtype=torch.float32)
+            start_l, start_p = X[self.landmarks.to(self.device)], X[self.placed.to(self.device)]
+        X_l = self.landmark_problem.embed(start_l, **solver_args)
+        self.placement = DensePlacement(self._landmark_data, X_l, _take_rows(self._data, self.placed),
+                                        loss=self.loss, metric=self.metric, device=self.device)
+        X_p = self.placement.embed(start_p, **solver_args)
+        out = torch.empty((self.n_items, self.embedding_dim), dtype=torch.float32, device=self.device)
+        out[self.landmarks.to(self.device)] = X_l
+        out[self.placed.to(self.device)] = X_p
+        self.X = constraints.Centered().project_onto_constraint(out, inplace=True)
+        self.value = self.placement.value
+        self.solve_stats = LandmarkSolveStats(self.landmark_problem.solve_stats, self.placement.solve_stats)
         return self.X

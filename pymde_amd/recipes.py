@@ -135,7 +135,8 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
-                       max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False):
+                       max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False,
+                       landmarks=None):
     """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
@@ -151,7 +152,18 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     ``metric="manhattan"`` is a ``ValueError``.  ``Standardized()`` rescales the deviations as above, with
     their rms over all pairs from one ``quality.pair_moments`` pass.  With ``Anchored`` no pair is removed:
     the anchor-anchor pairs add a constant to the value of the problem and nothing to the gradient of the free
-    rows."""
+    rows.
+
+    ``landmarks=m`` (``2 <= m < n``; implies the dense path) returns a ``dense.LandmarkMDE``: landmark MDS.  ``m``
+    rows, drawn uniformly without replacement from ``seed``, are embedded with a ``DenseMDE`` over all their pairs
+    and every other row is placed against them with a ``DensePlacement`` -- O(m^2 + n m) pairs per sweep instead
+    of O(n^2), which is how all-pairs distance preservation reaches a million rows.  ``constraint`` must be
+    ``None`` or ``Centered()``: the placed rows are unconstrained, so ``Standardized`` and ``Anchored`` are a
+    ``ValueError``.  ``max_distances`` is not consulted.  Score the result with
+    ``quality.stress(data, X, sample=...)``."""
+    if landmarks is not None:
+        return _dense.LandmarkMDE(data, landmarks, embedding_dim=embedding_dim, loss=loss, constraint=constraint,
+                                  metric=metric, seed=seed, device=device)
     if dense:
         return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric)
     metric = _metrics.resolve(metric)
