@@ -420,6 +420,49 @@ int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, co
                         const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC, int32_t kind,
                         float s0, float s1, float s2, int32_t slices, double* loss, float* grad, double* row_loss,
                         void* work, void* stream);
+/* mde_pair_loss_cross over a LIST of query rows, what the per-row placement solver evaluates.
+ * The arguments of mde_pair_loss_cross, then rows [n_rows] (int32, on the device): distinct query rows in any order;
+ * NULL means all of them in order and requires n_rows == n_q.  1 <= n_rows <= n_q; the entries are not checked.
+ * Workgroup x owns the list entries 64 x ... 64 x + 63 and reads Q, the row norms, XQ and the Dm row through the
+ * list.  For every listed row i, written at the row's own index (the rows not listed are not written):
+ *   row_loss double [n_q]     = sum_j l(E_ij, D_ij)
+ *   row_grad float [n_q, d]   = (1 / n_c) sum_j (l'(E_ij) / E_ij) (xq_i - xc_j), rounded once from double
+ * the gradient of the row's own mean loss row_loss[i] / n_c: it is divided by n_c, not by n_q n_c, so a row's result
+ * does not depend on the list.  There is no loss total.  The same column order and the same fixed-order double sums
+ * as mde_pair_loss_cross: at the same slice count row_loss holds the bits of that call.  slices == 0 resolves the
+ * automatic count from the list's length (a short list still fills the device), so there the bits depend on n_rows.
+ * work: mde_pair_loss_cross_rows_work_bytes(n_q, n_c, d, slices) bytes, enough for every list length.  ASYNC. */
+int64_t mde_pair_loss_cross_rows_work_bytes(int64_t n_q, int64_t n_c, int32_t d, int32_t slices);
+int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                             const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
+                             int32_t kind, float s0, float s1, float s2, int32_t slices, int64_t n_rows,
+                             const int32_t* rows, double* row_loss, float* row_grad, void* work, void* stream);
+/* The per-row solver of a separable problem (csrc/mde_rows.hip): n independent d-dimensional
+ * minimisations (1 <= d <= 8) advanced in lock step, one BFGS iteration with a backtracking line search per row and
+ * call.  State, all on the device: x [n, d], g [n, d], p [n, d], t [n] float; H [n, d, d] float (the inverse-Hessian
+ * estimate); f [n] double; flags [n] int32 (bits 0-1 the status below, bit 2 "fresh": H is the identity it was reset
+ * to, bits 3.. the accepted steps in a row that lowered f by at most 1e-7 |f|).  The objective of row i is
+ * f_i = row_loss[i] / n_c with gradient row_grad[i, :], as mde_pair_loss_cross_rows writes them.
+ *   mde_rows_init   from the evaluation at x: H = I, p = -g, t = min(1, 1 / |g|_1), fresh; a row with |g|_2 <= eps
+ *                   is converged (one whose f or g is not finite is stalled).
+ *   mde_rows_step   from the evaluation at x_trial, for every active row: accept when f_t and g_t are finite and
+ *                   f_t <= f + 1e-4 t g.p -- BFGS update with (s, y) when s.y > 1e-10 |s| |y| (a fresh H is first
+ *                   scaled to (s.y / y.y) I), adopt x, f, g; converged when |g|_2 <= eps; stalled when x_trial == x
+ *                   or after two small decreases in a row; otherwise p = -H g (reset to H = I, p = -g when g.p >= 0)
+ *                   and t = 1 -- else reject: t <- clamp(-g.p t^2 / (2 (f_t - f - g.p t)), 0.1 t, 0.5 t) (0.5 t when
+ *                   the denominator is not positive and finite); stalled when t max|p| <= 1e-10 max(1, max|x|).
+ * Both then write x_trial = x + t p for the active rows and x_trial = x for all others, whose state is not touched,
+ * and counts int64 [3] = the number of rows in each status.  Float32 state; the inner products, the Armijo test and
+ * the update are formed in double.  Integer atomics on counts only: the same bits on every run.  ASYNC. */
+#define MDE_ROWS_ACTIVE 0
+#define MDE_ROWS_CONVERGED 1
+#define MDE_ROWS_STALLED 2
+int mde_rows_init(int64_t n, int32_t d, int64_t n_c, float eps, const float* x, const double* row_loss,
+                  const float* row_grad, double* f, float* g, float* H, float* p, float* t, int32_t* flags,
+                  float* x_trial, int64_t* counts, void* stream);
+int mde_rows_step(int64_t n, int32_t d, int64_t n_c, float eps, float* x, double* f, float* g, float* H, float* p,
+                  float* t, int32_t* flags, float* x_trial, const double* row_loss, const float* row_grad,
+                  int64_t* counts, void* stream);
 /* Metrics other than Euclidean on the original data (csrc/mde_metric.hip); definitions as in
  * scipy.spatial.distance.  The reference has no metric keyword. */
 #define MDE_METRIC_EUCLIDEAN 0

@@ -99,6 +99,13 @@ SYMBOLS = {
     "mde_pair_loss_cross_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "mde_pair_loss_cross": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp, c_i32,
                                     c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_pair_loss_cross_rows_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "mde_pair_loss_cross_rows": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp,
+                                         c_i32, c_f32, c_f32, c_f32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_rows_init": (c_i32, [c_i64, c_i32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                              c_vp, c_vp]),
+    "mde_rows_step": (c_i32, [c_i64, c_i32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                              c_vp, c_vp]),
     "mde_ann_search": (c_i32, [c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
                                c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_ann_centroids": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),

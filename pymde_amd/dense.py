@@ -28,6 +28,7 @@ from pymde_amd import optim
 from pymde_amd import preprocess
 from pymde_amd import problem as _problem
 from pymde_amd import quality
+from pymde_amd import rows as _rows
 from pymde_amd import util
 from pymde_amd.functions import function as _function
 from pymde_amd.functions import losses
@@ -395,9 +396,15 @@ class DensePlacement(DenseMDE):
     both spaces is an ordinary pair (D = E = 0).
 
     ``embed()`` starts, by default, every new row at the mean of the embedding vectors of its ``d + 1`` nearest old
-    rows (``d + 1`` points fix a position in R^d; perturbed by 1e-4 if a new row lands exactly on an old one), and
-    runs ONE L-BFGS over all new rows, although the objective is separable over them.  After it: ``X`` (the new
-    rows, [n_new, d]), ``solve_stats``, ``value`` and ``residual_norm``; ``embedding()`` is ``cat([X_old, X_new])``."""
+    rows (``d + 1`` points fix a position in R^d; perturbed by 1e-4 if a new row lands exactly on an old one).  The
+    objective is separable over the new rows, and ``embed`` has two solvers for it.  ``solver="joint"`` (the default)
+    runs ONE L-BFGS over all new rows: one step length and one set of curvature pairs for rows that do not interact.
+    ``solver="rows"`` (``pymde_amd.rows``) runs a BFGS with its own line search and its own
+    stopping test for every row, all rows in lock step, and evaluates only the rows that are still working; it ends
+    when every row has converged (``|g_i| <= eps``, which implies the joint criterion) or stalled.  After either:
+    ``X`` (the new rows, [n_new, d]), ``solve_stats``, ``value`` and ``residual_norm``; after ``"rows"`` also
+    ``row_status`` (int32 [n_new]: 0 still active when ``max_iter`` ran out, 1 converged, 2 stalled).
+    ``embedding()`` is ``cat([X_old, X_new])``."""
 
     def __init__(self, data, X, new_data, loss=losses.Absolute, metric="euclidean", deviation_scale=1.0,
                  distance_matrix=None, device=None):
@@ -476,7 +483,9 @@ class DensePlacement(DenseMDE):
         self.solve_stats = None
         self.value = None
         self.residual_norm = None
+        self.row_status = None
         self._work_buffer = None
+        self._rows_work_buffer = None
 
     def __str__(self):
         source = "data matrices, metric %s" % self.metric if self._A is not None else "distance matrix"
@@ -521,14 +530,45 @@ class DensePlacement(DenseMDE):
             X_new = X_new + 1e-4 * torch.randn(X_new.shape, device=self.device, dtype=X_new.dtype)
         return X_new.contiguous()
 
+    def _evaluate_rows(self, X, rows, row_loss, row_grad):
+        """``mde_pair_loss_cross_rows`` at a float32 X: the sums of the rows of ``rows`` (``None``: all), in place."""
+        if self._rows_work_buffer is None:
+            with torch.cuda.device(self.device):
+                self._rows_work_buffer = _rows.work_cross_rows(_lib.load(), self.n_items, self.n_old,
+                                                               self.embedding_dim, 0, self.device)
+        return _rows.pair_loss_cross_rows(X.contiguous(), self._X_old, self._spec, row_loss, row_grad, rows=rows,
+                                          Q=self._Q, C=self._A, mode=self._mode, Dm=self._Dm,
+                                          d_scale=self.deviation_scale, work=self._rows_work_buffer)
+
     def embed(self, X=None, eps=1e-5, max_iter=300, memory_size=10, verbose=False, print_every=None,
-              snapshot_every=None):
+              snapshot_every=None, solver="joint"):
         """Place the new rows; stores them in ``self.X`` [n_new, d] and returns them.  ``X``: their start (default:
-        ``initialization()``).  Other arguments as in ``MDE.embed``."""
+        ``initialization()``).  ``solver``: ``"joint"``, one L-BFGS over all rows, or ``"rows"``, a BFGS per row
+        (``pymde_amd.rows``; ``max_iter`` then counts sweeps, ``eps`` bounds every row's own gradient norm, and
+        ``memory_size`` is not used: a row keeps a full d x d matrix).  Other arguments as in ``MDE.embed``."""
+        _rows.check_solver(solver)
+        if max_iter < 0:
+            raise ValueError("`max_iter` must be greater than 0")
         if X is None:
             X = self.initialization()
-        return super().embed(X, eps=eps, max_iter=max_iter, memory_size=memory_size, verbose=verbose,
-                             print_every=print_every, snapshot_every=snapshot_every)
+        if solver == "joint":
+            return super().embed(X, eps=eps, max_iter=max_iter, memory_size=memory_size, verbose=verbose,
+                                 print_every=print_every, snapshot_every=snapshot_every)
+        X = self._embedding_arg(X).detach().contiguous()
+        if verbose:
+            _problem.LOGGER.info(f"Placing {self.n_items} rows in R^{self.embedding_dim} against {self.n_old} "
+                                 f"embedded rows, each row on its own: eps={eps:.1e}, max_iter={max_iter}")
+        result = _rows.solve(self._evaluate_rows, X, self.n_old, eps=eps, max_iter=max_iter,
+                             snapshot_every=snapshot_every, verbose=verbose, print_every=print_every,
+                             logger=_problem.LOGGER)
+        self.X, self.solve_stats, self.row_status = result.X, result.solve_stats, result.row_status
+        self.value, self.residual_norm = result.value, result.residual_norm
+        if verbose:
+            _problem.LOGGER.info(f"Finished placing in {result.solve_stats.solve_time:.3f} seconds and "
+                                 f"{result.solve_stats.iterations} sweeps ({result.solve_stats.evaluations:.1f} full "
+                                 f"evaluations): average distortion {self.value:.3g} | residual norm "
+                                 f"{self.residual_norm:.1e}")
+        return self.X
 
     def embedding(self, X=None):
         """``cat([X_old, X_new])`` [n_old + n_new, d]: the embedded rows, bit for bit, then the placed ones."""
@@ -610,10 +650,12 @@ class LandmarkMDE(object):
         self.value = None
         self.solve_stats = None
 
-    def embed(self, X=None, **solver_args):
+    def embed(self, X=None, placement_solver="joint", **solver_args):
         """Embed the landmarks, place the other rows, centre the whole: stores the [n, d] embedding in ``self.X`` and
         returns it.  ``X``: an optional [n, d] start for both stages; ``solver_args`` as in ``DenseMDE.embed``, for
-        both stages."""
+        both stages; ``placement_solver`` (``"joint"`` or ``"rows"``) is the ``solver`` of ``DensePlacement.embed``,
+        for the placement stage only."""
+        _rows.check_solver(placement_solver, "placement_solver")
         start_l = start_p = None
         if X is not None:
             if tuple(X.shape) != (self.n_items, self.embedding_dim):
@@ -624,7 +666,7 @@ class LandmarkMDE(object):
         X_l = self.landmark_problem.embed(start_l, **solver_args)
         self.placement = DensePlacement(self._landmark_data, X_l, _take_rows(self._data, self.placed),
                                         loss=self.loss, metric=self.metric, device=self.device)
-        X_p = self.placement.embed(start_p, **solver_args)
+        X_p = self.placement.embed(start_p, solver=placement_solver, **solver_args)
         out = torch.empty((self.n_items, self.embedding_dim), dtype=torch.float32, device=self.device)
         out[self.landmarks.to(self.device)] = X_l
         out[self.placed.to(self.device)] = X_p
