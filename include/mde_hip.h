@@ -437,6 +437,56 @@ int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, const float* 
                              const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
                              int32_t kind, float s0, float s1, float s2, int32_t slices, int64_t n_rows,
                              const int32_t* rows, double* row_loss, float* row_grad, void* work, void* stream);
+/* Per-pair weights and missing pairs for the three calls above.  Each *_weighted call takes the
+ * arguments of its namesake, then the weight source `wsource`, `p`, `W` and (not the list call) `pairs`:
+ *   MDE_PAIR_W_NONE     no weights: the namesake's arithmetic, with `pairs` as the divisor.  W NULL.
+ *   MDE_PAIR_W_POWER    w = D^-p from the pair's own D = d_scale * deviation, formed in the kernel: no per-pair array,
+ *                       either source of D.  p = 2 is 1.0f / (D * D), the bits of the losses' default weights; p = 1
+ *                       is one IEEE division; p = 0 is exactly 1; any other finite p >= 0 is powf(D, -p).  D = 0 is not
+ *                       special: it gives what these expressions give.  W NULL.
+ *   MDE_PAIR_W_MATRIX   w = W[i][j], a row-major float32 matrix on the device, [n, n] for mde_pair_loss_weighted (both
+ *                       triangles are read; it is expected to be symmetric; the diagonal is never used) and [n_q, n_c]
+ *                       for the rectangular calls, with either source of D.  Only w > 0 counts: w == 0 is a MISSING
+ *                       pair, skipped before anything of it is evaluated, so its Dm entry may be NaN or infinite.
+ *                       p is ignored (but checked).
+ * For MDE_F_L_WEIGHTED_QUADRATIC and MDE_F_L_WEIGHTED_POWER w takes the place of a1 (the reference's
+ * WeightedQuadratic(deviations, weights)); for every other kind l and l'(E) / E are multiplied by w in float32, after
+ * the NaN / Inf -> 1 rule.  `pairs` (double, > 0) is the number of pairs that count:
+ *   mde_pair_loss_weighted         loss = sum_i row_loss[i] / (2 pairs), grad = G / pairs
+ *   mde_pair_loss_cross_weighted   loss = sum_i row_loss[i] / pairs,     grad = G / pairs
+ *   mde_pair_loss_cross_rows_weighted   row_grad = G / n_c as in mde_pair_loss_cross_rows: it has no `pairs`.
+ * The same grid, work buffers (the namesakes' *_work_bytes), double sums and fixed order: the same bits on every run,
+ * and with MDE_PAIR_W_NONE and the namesake's pair count the namesake's bits.  MDE_E_INVALID with a message, before any
+ * launch, for an unknown source, W non-null without MDE_PAIR_W_MATRIX (both sources given) or NULL with it, p
+ * negative or not finite, pairs not positive and finite, and whatever the namesake refuses.  ASYNC. */
+#define MDE_PAIR_W_NONE 0
+#define MDE_PAIR_W_POWER 1
+#define MDE_PAIR_W_MATRIX 2
+int mde_pair_loss_weighted(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale,
+                           int32_t d, const float* X, int32_t kind, float s0, float s1, float s2, int32_t slices,
+                           int32_t wsource, float p, const float* W, double pairs, double* loss, float* grad,
+                           double* row_loss, void* work, void* stream);
+int mde_pair_loss_cross_weighted(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                                 const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
+                                 int32_t kind, float s0, float s1, float s2, int32_t slices, int32_t wsource, float p,
+                                 const float* W, double pairs, double* loss, float* grad, double* row_loss, void* work,
+                                 void* stream);
+int mde_pair_loss_cross_rows_weighted(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                                      int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                                      const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
+                                      int64_t n_rows, const int32_t* rows, int32_t wsource, float p, const float* W,
+                                      double* row_loss, float* row_grad, void* work, void* stream);
+/* One pass over a weight matrix W [n_q, n_c] (square != 0: n_q == n_c, the diagonal is ignored) and, when Dm is not
+ * NULL, over the deviations it weighs.  A pair is KEPT when its w > 0.
+ *   counts int64 [5]   0 entries of W that are NaN or infinite | 1 entries that are negative | 2 kept pairs (square: of
+ *                      the strict upper triangle; rectangular: all) | 3 rows without a kept pair | 4 kept entries whose
+ *                      Dm is NaN, infinite or negative (square: of both triangles, as the walk reads both)
+ *   tops float [4]     square only (0 otherwise): 0 max |W - W^T| | 1 max |W|, both over the finite off-diagonal
+ *                      entries | 2 max |Dm - Dm^T| | 3 max Dm, both over the kept entries with a valid Dm
+ *   row_kept int32 [n_q]   the kept pairs of every row (square: over j != i)
+ * Integer counters only; the results do not depend on the order of the work.  The call clears its outputs.  ASYNC. */
+int mde_pair_weights_check(int64_t n_q, int64_t n_c, int32_t square, const float* W, const float* Dm, int64_t* counts,
+                           float* tops, int32_t* row_kept, void* stream);
 /* The per-row solver of a separable problem (csrc/mde_rows.hip): n independent d-dimensional
  * minimisations (1 <= d <= 8) advanced in lock step, one BFGS iteration with a backtracking line search per row and
  * call.  State, all on the device: x [n, d], g [n, d], p [n, d], t [n] float; H [n, d, d] float (the inverse-Hessian

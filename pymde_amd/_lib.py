@@ -102,6 +102,15 @@ SYMBOLS = {
     "mde_pair_loss_cross_rows_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "mde_pair_loss_cross_rows": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp,
                                          c_i32, c_f32, c_f32, c_f32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_pair_loss_weighted": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32,
+                                       c_i32, c_i32, c_f32, c_vp, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_pair_loss_cross_weighted": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_vp,
+                                             c_i32, c_f32, c_f32, c_f32, c_i32, c_i32, c_f32, c_vp, ctypes.c_double, c_vp, c_vp,
+                                             c_vp, c_vp, c_vp]),
+    "mde_pair_loss_cross_rows_weighted": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp,
+                                                  c_vp, c_i32, c_f32, c_f32, c_f32, c_i32, c_i64, c_vp, c_i32, c_f32,
+                                                  c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_pair_weights_check": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_rows_init": (c_i32, [c_i64, c_i32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp]),
     "mde_rows_step": (c_i32, [c_i64, c_i32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

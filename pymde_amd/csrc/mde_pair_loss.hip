@@ -35,6 +35,12 @@
 // placement solver (mde_rows.hip) evaluates once its first rows have finished: workgroup x owns the list entries
 // 64 x ..., reads Q, the row norms, XQ and the Dm row through the list (ROWS = true, a compile-time variant of
 // k_pair_loss_walk), and k_pair_loss_fold_rows writes row_loss and row_grad = G / n_c at the rows' own indices.
+//
+// mde_pair_loss_weighted, mde_pair_loss_cross_weighted and mde_pair_loss_cross_rows_weighted are
+// the three calls with a weight per pair -- D^-p formed here, or a matrix W whose zeros are MISSING pairs (WSRC, another
+// compile-time variant of k_pair_loss_walk) -- and with the number of pairs that count passed in.  The unweighted calls
+// launch the WSRC = PAIR_W_NONE instantiations, which are what they were.  mde_pair_weights_check, at the end, is the
+// one pass over W that pymde_amd.dense validates it with.
 #include <math.h>
 
 #include "mde_pair.h"
@@ -43,10 +49,35 @@
 #define PAIR_LOSS_MAX_D 8
 #define PAIR_LOSS_XS (KNN_BN * PAIR_LOSS_MAX_D)   // floats of the staged column rows of X: 2 KB
 
+// The weight of a pair, a compile-time variant of the walk like ROWS:
+//   PAIR_W_NONE    what the walk was: the weighted kinds get a1 = 1 / D^2, nothing else is weighted;
+//   PAIR_W_POWER   w = D^-p from the pair's own D (after d_scale): no per-pair array, either source of D;
+//   PAIR_W_MATRIX  w = W[i][j], a row-major float32 matrix shaped like Dm, whose 64x64 tile is loaded as the Dm
+//                  tile is and parked in the idle tile after sD; w == 0 is a MISSING pair: it is skipped before its D
+//                  (which may be NaN or infinite in a matrix) is looked at.
+// For the weighted kinds w takes the place of a1; for every other kind f and gd are multiplied by w in float32.
+#define PAIR_W_NONE MDE_PAIR_W_NONE
+#define PAIR_W_POWER MDE_PAIR_W_POWER
+#define PAIR_W_MATRIX MDE_PAIR_W_MATRIX
+struct PairWeights {
+  const float* W;   // PAIR_W_MATRIX: [n_q, n_c] (the square problem: [n, n])
+  float p;          // PAIR_W_POWER: the exponent
+  int pclass;       // PAIR_W_POWER: 0, 1, 2 for p == 0, 1, 2 (exact forms), 3 for powf
+};
+
+// D^-p.  p = 2 is the expression of the losses' default weights (the same bits), p = 1 one IEEE division, p = 0
+// exactly 1; D = 0 gives what these expressions give (+inf for p > 0), as the default weights do.
+__device__ __forceinline__ float pair_power_weight(float D, int pclass, float p) {
+  if (pclass == 2) return 1.0f / (D * D);
+  if (pclass == 1) return 1.0f / D;
+  if (pclass == 0) return 1.0f;
+  return powf(D, -p);
+}
+
 // ROWS (mde_pair_loss_cross_rows): the workgroup's 64 rows are the list entries 64 x ... of `rows` (NULL: the rows
 // themselves), n_q is the length of the list, and the partials are indexed by list position.  Without ROWS `rows`
 // is not read and the code is what it was.
-template <int DC, bool MATRIX, bool SELF, bool ROWS = false>
+template <int DC, bool MATRIX, bool SELF, bool ROWS = false, int WSRC = PAIR_W_NONE>
 __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, int nf, int d, int mode,
                                                               int64_t slice_cols, const float* __restrict__ Q,
                                                               const float* __restrict__ qn,
@@ -57,10 +88,12 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
                                                               const float* __restrict__ XC, int kind, int weighted,
                                                               MdeScalars S, float d_scale,
                                                               double* __restrict__ part,
-                                                              const int32_t* __restrict__ rows) {
+                                                              const int32_t* __restrict__ rows, PairWeights wt) {
   static_assert(!(SELF && ROWS), "the row list belongs to the rectangular walk");
+  constexpr bool WMAT = WSRC == PAIR_W_MATRIX;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const knn_tile_lds s = knn_tile_carve(lds, 0, PAIR_TILE + PAIR_LOSS_XS + (ROWS ? KNN_BM : 0));
+  float* sW = s.extra;                                          // [KNN_BM][KNN_BN + 1] the weights of the tile (WMAT)
   float* sX = s.extra + PAIR_TILE;                              // [KNN_BN][DC]
   const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
   const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
@@ -93,6 +126,22 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
     auto keep = [&](int rr, int cc) {
       return row0 + rr < n_q && col0 + cc < n_c && (!SELF || row0 + rr != col0 + cc);
     };
+    // the tile of W: loaded and parked as the Dm tile below is; what the tile does not have gets the weight 0
+    float wv[WMAT ? KNN_BM / 4 : 1];
+    auto load_w = [&]() {
+      const int lane = tid & 63;
+      const int64_t gc = col0 + lane < n_c ? col0 + lane : n_c - 1;
+#pragma unroll
+      for (int q = 0; q < KNN_BM / 4; ++q) {
+        const int64_t gr = ROWS ? row_of(w + 4 * q) : (row0 + w + 4 * q < n_q ? row0 + w + 4 * q : n_q - 1);
+        wv[q] = wt.W[gr * (int64_t)n_c + gc];
+      }
+    };
+    auto park_w = [&]() {
+      const int lane = tid & 63;
+#pragma unroll
+      for (int q = 0; q < KNN_BM / 4; ++q) sW[(w + 4 * q) * (KNN_BN + 1) + lane] = keep(w + 4 * q, lane) ? wv[q] : 0.0f;
+    };
     if constexpr (MATRIX) {
       // wave w takes the tile rows w, w + 4, ...: all sixteen loads go out from clamped addresses before the first is
       // used, and what the tile does not have (or the diagonal of the square walk) is replaced when the registers are
@@ -105,10 +154,12 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
         const int64_t gr = ROWS ? row_of(w + 4 * q) : (row0 + w + 4 * q < n_q ? row0 + w + 4 * q : n_q - 1);
         v[q] = Dm[gr * (int64_t)n_c + gc];
       }
+      if constexpr (WMAT) load_w();
       __syncthreads();                                          // the walk of the last tile is over
 #pragma unroll
       for (int q = 0; q < KNN_BM / 4; ++q)
         s.sD[(w + 4 * q) * (KNN_BN + 1) + lane] = keep(w + 4 * q, lane) ? v[q] : PAIR_FLT_MAX;
+      if constexpr (WMAT) park_w();
     } else {
       const float* acol[KNN_STG];
       bool cok[KNN_STG];
@@ -121,6 +172,27 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
       // the park follows the barriers of knn_gram_tile: every thread is past the walk of the last tile by then
       const f32x16 acc = knn_gram_tile(s.sA, s.sB, nf, arow, qok, acol, cok);
       knn_park_tile(s.sD, acc, keep, [&](int rr) { return qn[row_of(rr)]; }, [&](int cc) { return cn[col0 + cc]; });
+      // (the tile of W in four batches of four rows, after the Gram tile: sixteen loads held over the tile's feature
+      // loop cost its occupancy)
+      if constexpr (WMAT) {
+        const int lane = tid & 63;
+        const int64_t gc = col0 + lane < n_c ? col0 + lane : n_c - 1;
+#pragma unroll 1
+        for (int q0 = 0; q0 < KNN_BM / 4; q0 += 4) {
+          float b[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int rr = w + 4 * (q0 + q);
+            const int64_t gr = ROWS ? row_of(rr) : (row0 + rr < n_q ? row0 + rr : n_q - 1);
+            b[q] = wt.W[gr * (int64_t)n_c + gc];
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int rr = w + 4 * (q0 + q);
+            sW[rr * (KNN_BN + 1) + lane] = keep(rr, lane) ? b[q] : 0.0f;
+          }
+        }
+      }
     }
     for (int i = tid; i < KNN_BN * DC; i += MDE_BLOCK) {
       const int c = i / DC, k = i - c * DC;
@@ -129,10 +201,17 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
     __syncthreads();
     const float* pd = s.sD + r * (KNN_BN + 1) + w * PAIR_COLS;
     const float* px = sX + w * PAIR_COLS * DC;
+    const float* pw = sW + r * (KNN_BN + 1) + w * PAIR_COLS;
 #pragma unroll 4
     for (int cc = 0; cc < PAIR_COLS; ++cc) {
       const float v = pd[cc];
-      if (v != PAIR_FLT_MAX) {                                  // what keep() refused is parked as FLT_MAX
+      float wgt = 0.0f;
+      bool counts = v != PAIR_FLT_MAX;                          // what keep() refused is parked as FLT_MAX
+      if constexpr (WMAT) {
+        wgt = pw[cc];                                           // ... and with the weight 0
+        counts = counts && wgt > 0.0f;                          // a missing pair: its D is never evaluated
+      }
+      if (counts) {
         const float D = (MATRIX ? v : pair_dist(v, mode)) * d_scale;
         float diff[DC], ss = 0.0f;
 #pragma unroll
@@ -140,10 +219,22 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
           diff[k] = xi[k] - px[cc * DC + k];
           ss = fmaf(diff[k], diff[k], ss);
         }
-        const float a1 = weighted ? 1.0f / (D * D) : 0.0f;      // the losses' default weights
+        float a1;
+        if constexpr (WSRC == PAIR_W_NONE) {
+          a1 = weighted ? 1.0f / (D * D) : 0.0f;                // the losses' default weights
+        } else {
+          if constexpr (WSRC == PAIR_W_POWER) wgt = pair_power_weight(D, wt.pclass, wt.p);
+          a1 = weighted ? wgt : 0.0f;                           // WeightedQuadratic(deviations, weights)
+        }
         float f, gd;
         mde_eval_rt(kind, ss, D, a1, S, f, gd);
         gd = mde_fix_g(gd);
+        if constexpr (WSRC != PAIR_W_NONE) {
+          if (!weighted) {
+            f *= wgt;
+            gd *= wgt;
+          }
+        }
         sl += (double)f;
 #pragma unroll
         for (int k = 0; k < DC; ++k) sg[k] = fma((double)gd, (double)diff[k], sg[k]);
@@ -263,19 +354,35 @@ extern "C" int64_t mde_pair_loss_cross_work_bytes(int64_t n_q, int64_t n_c, int3
   return s * n_q * (1 + d) * 8 + 4 * (n_q + n_c);
 }
 
-template <int DC, bool SELF, bool ROWS>
+template <int DC, bool SELF, bool ROWS, int WSRC>
 static void pair_loss_launch_dc(bool matrix, dim3 grid, hipStream_t st, int n_q, int n_c, int nf, int d, int mode,
                                 int64_t slice_cols, const float* Q, const float* qn, const float* C, const float* cn,
                                 const float* Dm, const float* XQ, const float* XC, int kind, MdeScalars S,
-                                float d_scale, double* part, const int32_t* rows) {
+                                float d_scale, double* part, const int32_t* rows, PairWeights wt) {
   const size_t lds = knn_tile_lds_bytes(0, PAIR_TILE + PAIR_LOSS_XS + (ROWS ? KNN_BM : 0));
   const int weighted = kind == MDE_F_L_WEIGHTED_QUADRATIC || kind == MDE_F_L_WEIGHTED_POWER;
   if (matrix)
-    hipLaunchKernelGGL((k_pair_loss_walk<DC, true, SELF, ROWS>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf, d, mode,
-                       slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part, rows);
+    hipLaunchKernelGGL((k_pair_loss_walk<DC, true, SELF, ROWS, WSRC>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf, d,
+                       mode, slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part, rows, wt);
   else
-    hipLaunchKernelGGL((k_pair_loss_walk<DC, false, SELF, ROWS>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf, d, mode,
-                       slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part, rows);
+    hipLaunchKernelGGL((k_pair_loss_walk<DC, false, SELF, ROWS, WSRC>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf,
+                       d, mode, slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part, rows, wt);
+}
+
+template <int DC, bool SELF, bool ROWS>
+static void pair_loss_launch_w(int wsrc, bool matrix, dim3 grid, hipStream_t st, int n_q, int n_c, int nf, int d,
+                               int mode, int64_t slice_cols, const float* Q, const float* qn, const float* C,
+                               const float* cn, const float* Dm, const float* XQ, const float* XC, int kind,
+                               MdeScalars S, float d_scale, double* part, const int32_t* rows, PairWeights wt) {
+  if (wsrc == PAIR_W_MATRIX)
+    pair_loss_launch_dc<DC, SELF, ROWS, PAIR_W_MATRIX>(matrix, grid, st, n_q, n_c, nf, d, mode, slice_cols, Q, qn, C,
+                                                       cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
+  else if (wsrc == PAIR_W_POWER)
+    pair_loss_launch_dc<DC, SELF, ROWS, PAIR_W_POWER>(matrix, grid, st, n_q, n_c, nf, d, mode, slice_cols, Q, qn, C,
+                                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
+  else
+    pair_loss_launch_dc<DC, SELF, ROWS, PAIR_W_NONE>(matrix, grid, st, n_q, n_c, nf, d, mode, slice_cols, Q, qn, C, cn,
+                                                     Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
 }
 
 // The walk of either problem on checked arguments: n_q rows (ROWS: list entries, the rows of `rows`) against the n_c
@@ -284,25 +391,44 @@ template <bool SELF, bool ROWS>
 static int pair_loss_walk(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* qn, const float* C,
                           const float* cn, int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
                           const float* XC, int32_t kind, MdeScalars S, int64_t s, double* part, const int32_t* rows,
-                          hipStream_t st) {
+                          int wsrc, PairWeights wt, hipStream_t st) {
   const int64_t tiles = (n_c + KNN_BN - 1) / KNN_BN;
   const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;     // whole tiles; the last slices may be short or empty
   const dim3 grid((unsigned)((n_q + KNN_BM - 1) / KNN_BM), (unsigned)s);
   const bool matrix = Dm != nullptr;
   if (d == 1)
-    pair_loss_launch_dc<1, SELF, ROWS>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C, cn,
-                                       Dm, XQ, XC, kind, S, d_scale, part, rows);
+    pair_loss_launch_w<1, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
+                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
   else if (d == 2)
-    pair_loss_launch_dc<2, SELF, ROWS>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C, cn,
-                                       Dm, XQ, XC, kind, S, d_scale, part, rows);
+    pair_loss_launch_w<2, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
+                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
   else if (d == 3)
-    pair_loss_launch_dc<3, SELF, ROWS>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C, cn,
-                                       Dm, XQ, XC, kind, S, d_scale, part, rows);
+    pair_loss_launch_w<3, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
+                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
   else
-    pair_loss_launch_dc<PAIR_LOSS_MAX_D, SELF, ROWS>(matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q,
-                                                     qn, C, cn, Dm, XQ, XC, kind, S, d_scale, part, rows);
+    pair_loss_launch_w<PAIR_LOSS_MAX_D, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode,
+                                                    slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, S, d_scale, part,
+                                                    rows, wt);
   MDE_LAUNCH_CHECK();
   return MDE_OK;
+}
+
+// The weight arguments of the *_weighted entry points; `pairs` < 0 where the entry point has none.
+static bool pair_weights_ok(const char* fn, int32_t wsrc, float p, const float* W, bool has_pairs, double pairs) {
+  const bool source_ok = wsrc == PAIR_W_NONE || wsrc == PAIR_W_POWER || wsrc == PAIR_W_MATRIX;
+  const bool w_ok = wsrc == PAIR_W_MATRIX ? W != nullptr : W == nullptr;
+  if (source_ok && w_ok && p >= 0.0f && isfinite(p) && (!has_pairs || (pairs > 0.0 && isfinite(pairs)))) return true;
+  mde_set_error("%s: invalid weights (the source is MDE_PAIR_W_NONE, MDE_PAIR_W_POWER or MDE_PAIR_W_MATRIX; W is "
+                "non-null under MDE_PAIR_W_MATRIX and NULL otherwise: one source, not both; p is finite and >= 0%s)",
+                fn, has_pairs ? "; pairs is finite and > 0" : "");
+  return false;
+}
+static PairWeights pair_weights(int32_t wsrc, float p, const float* W) {
+  PairWeights wt;
+  wt.W = wsrc == PAIR_W_MATRIX ? W : nullptr;
+  wt.p = p;
+  wt.pclass = p == 0.0f ? 0 : p == 1.0f ? 1 : p == 2.0f ? 2 : 3;
+  return wt;
 }
 
 // The walk, the fold and the total of either problem on checked arguments: SELF is the square problem (rows and
@@ -310,10 +436,10 @@ static int pair_loss_walk(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, 
 template <bool SELF>
 static int pair_loss_run(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* qn, const float* C,
                          const float* cn, int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
-                         const float* XC, int32_t kind, MdeScalars S, int64_t s, double pairs, double* loss,
-                         float* grad, double* row_loss, double* part, hipStream_t st) {
+                         const float* XC, int32_t kind, MdeScalars S, int64_t s, int wsrc, PairWeights wt,
+                         double pairs, double* loss, float* grad, double* row_loss, double* part, hipStream_t st) {
   const int rc = pair_loss_walk<SELF, false>(n_q, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s,
-                                             part, nullptr, st);
+                                             part, nullptr, wsrc, wt, st);
   if (rc != MDE_OK) return rc;
   hipLaunchKernelGGL(k_pair_loss_fold, dim3(mde_grid(n_q * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_q,
                      (int)d, (int)s, pairs, part, row_loss, grad);
@@ -323,17 +449,20 @@ static int pair_loss_run(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, c
   return MDE_OK;
 }
 
-extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale,
-                             int32_t d, const float* X, int32_t kind, float s0, float s1, float s2, int32_t slices,
-                             double* loss, float* grad, double* row_loss, void* work, void* stream) {
+// The square problem behind mde_pair_loss (no weights, pairs = n (n - 1) / 2) and mde_pair_loss_weighted.
+static int pair_loss_square(const char* fn, int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm,
+                            float d_scale, int32_t d, const float* X, int32_t kind, float s0, float s1, float s2,
+                            int32_t slices, int32_t wsrc, float p, const float* W, double pairs, double* loss,
+                            float* grad, double* row_loss, void* work, void* stream) {
   const bool source_ok = (A != nullptr) != (Dm != nullptr) && (!A || (nf >= 1 && (mode == 0 || mode == 1)));
   if (!pair_loss_args_ok(n, d, slices) || !source_ok || !pair_loss_kind_ok(kind) || !(d_scale > 0.0f) ||
       !isfinite(d_scale) || !X || !loss || !grad || !row_loss || !work) {
-    mde_set_error("mde_pair_loss: invalid arguments (2 <= n < 2^31, 1 <= d <= %d, exactly one of A (nf >= 1, mode 0 / "
+    mde_set_error("%s: invalid arguments (2 <= n < 2^31, 1 <= d <= %d, exactly one of A (nf >= 1, mode 0 / "
                   "1) and Dm, kind one of the MDE_F_L_* losses, d_scale positive and finite, 0 <= slices <= %d, "
-                  "non-null X / outputs / work)", PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+                  "non-null X / outputs / work)", fn, PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
     return MDE_E_INVALID;
   }
+  if (!pair_weights_ok(fn, wsrc, p, W, true, pairs)) return MDE_E_INVALID;
   const int64_t s = cross_resolve_slices(n, n, slices);
   if (s < 0) return (int)s;
   double* part = static_cast<double*>(work);
@@ -343,26 +472,43 @@ extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode
     if (rc != MDE_OK) return rc;
   }
   const MdeScalars S = {s0, s1, s2};
-  const double pairs = 0.5 * (double)n * (double)(n - 1);
-  return pair_loss_run<true>(n, n, nf, A, an, A, an, mode, Dm, d_scale, d, X, X, kind, S, s, pairs, loss, grad,
-                             row_loss, part, mde_stream(stream));
+  return pair_loss_run<true>(n, n, nf, A, an, A, an, mode, Dm, d_scale, d, X, X, kind, S, s, wsrc,
+                             pair_weights(wsrc, p, W), pairs, loss, grad, row_loss, part, mde_stream(stream));
+}
+
+extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale,
+                             int32_t d, const float* X, int32_t kind, float s0, float s1, float s2, int32_t slices,
+                             double* loss, float* grad, double* row_loss, void* work, void* stream) {
+  return pair_loss_square("mde_pair_loss", n, nf, A, mode, Dm, d_scale, d, X, kind, s0, s1, s2, slices, PAIR_W_NONE,
+                          0.0f, nullptr, 0.5 * (double)n * (double)(n - 1), loss, grad, row_loss, work, stream);
+}
+
+// mde_pair_loss with a weight per pair and the count of the pairs that count passed in.
+extern "C" int mde_pair_loss_weighted(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm,
+                                      float d_scale, int32_t d, const float* X, int32_t kind, float s0, float s1,
+                                      float s2, int32_t slices, int32_t wsource, float p, const float* W, double pairs,
+                                      double* loss, float* grad, double* row_loss, void* work, void* stream) {
+  return pair_loss_square("mde_pair_loss_weighted", n, nf, A, mode, Dm, d_scale, d, X, kind, s0, s1, s2, slices,
+                          wsource, p, W, pairs, loss, grad, row_loss, work, stream);
 }
 
 // The rectangular problem: every (query row, corpus row) pair, a gradient for the query rows only.
-extern "C" int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
-                                   const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
-                                   int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
-                                   float* grad, double* row_loss, void* work, void* stream) {
+static int pair_loss_rect(const char* fn, int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                          int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
+                          int32_t kind, float s0, float s1, float s2, int32_t slices, int32_t wsrc, float p,
+                          const float* W, double pairs, double* loss, float* grad, double* row_loss, void* work,
+                          void* stream) {
   const bool gram = Q != nullptr && C != nullptr && Dm == nullptr;
   const bool matrix = Q == nullptr && C == nullptr && Dm != nullptr;
   const bool source_ok = matrix || (gram && nf >= 1 && (mode == 0 || mode == 1));
   if (!pair_loss_cross_args_ok(n_q, n_c, d, slices) || !source_ok || !pair_loss_kind_ok(kind) || !(d_scale > 0.0f) ||
       !isfinite(d_scale) || !XQ || !XC || !loss || !grad || !row_loss || !work) {
-    mde_set_error("mde_pair_loss_cross: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and C (nf "
+    mde_set_error("%s: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and C (nf "
                   ">= 1, mode 0 / 1) or Dm alone, kind one of the MDE_F_L_* losses, d_scale positive and finite, 0 <= "
-                  "slices <= %d, non-null XQ / XC / outputs / work)", PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+                  "slices <= %d, non-null XQ / XC / outputs / work)", fn, PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
     return MDE_E_INVALID;
   }
+  if (!pair_weights_ok(fn, wsrc, p, W, true, pairs)) return MDE_E_INVALID;
   const int64_t s = cross_resolve_slices(n_q, n_c, slices);
   if (s < 0) return (int)s;
   double* part = static_cast<double*>(work);
@@ -374,9 +520,27 @@ extern "C" int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const f
     if (rc != MDE_OK) return rc;
   }
   const MdeScalars S = {s0, s1, s2};
-  const double pairs = (double)n_q * (double)n_c;
-  return pair_loss_run<false>(n_q, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s, pairs, loss, grad,
-                              row_loss, part, mde_stream(stream));
+  return pair_loss_run<false>(n_q, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s, wsrc,
+                              pair_weights(wsrc, p, W), pairs, loss, grad, row_loss, part, mde_stream(stream));
+}
+
+extern "C" int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                                   const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
+                                   int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
+                                   float* grad, double* row_loss, void* work, void* stream) {
+  return pair_loss_rect("mde_pair_loss_cross", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0, s1, s2,
+                        slices, PAIR_W_NONE, 0.0f, nullptr, (double)n_q * (double)n_c, loss, grad, row_loss, work,
+                        stream);
+}
+
+// mde_pair_loss_cross with a weight per pair, W [n_q, n_c], and the count of the pairs that count passed in.
+extern "C" int mde_pair_loss_cross_weighted(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                                            int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                                            const float* XC, int32_t kind, float s0, float s1, float s2,
+                                            int32_t slices, int32_t wsource, float p, const float* W, double pairs,
+                                            double* loss, float* grad, double* row_loss, void* work, void* stream) {
+  return pair_loss_rect("mde_pair_loss_cross_weighted", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0,
+                        s1, s2, slices, wsource, p, W, pairs, loss, grad, row_loss, work, stream);
 }
 
 // The most list entries times slices the walk of mde_pair_loss_cross_rows can hold partials for, over every list
@@ -408,23 +572,24 @@ extern "C" int64_t mde_pair_loss_cross_rows_work_bytes(int64_t n_q, int64_t n_c,
 }
 
 // The rectangular problem over a list of query rows: per-row sums only, written at the rows' own indices.
-extern "C" int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
-                                        int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
-                                        const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
-                                        int64_t n_rows, const int32_t* rows, double* row_loss, float* row_grad,
-                                        void* work, void* stream) {
+static int pair_loss_rect_rows(const char* fn, int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                               int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                               const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
+                               int64_t n_rows, const int32_t* rows, int32_t wsrc, float p, const float* W,
+                               double* row_loss, float* row_grad, void* work, void* stream) {
   const bool gram = Q != nullptr && C != nullptr && Dm == nullptr;
   const bool matrix = Q == nullptr && C == nullptr && Dm != nullptr;
   const bool source_ok = matrix || (gram && nf >= 1 && (mode == 0 || mode == 1));
   const bool rows_ok = n_rows >= 1 && n_rows <= n_q && (rows != nullptr || n_rows == n_q);
   if (!pair_loss_cross_args_ok(n_q, n_c, d, slices) || !source_ok || !rows_ok || !pair_loss_kind_ok(kind) ||
       !(d_scale > 0.0f) || !isfinite(d_scale) || !XQ || !XC || !row_loss || !row_grad || !work) {
-    mde_set_error("mde_pair_loss_cross_rows: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and "
+    mde_set_error("%s: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and "
                   "C (nf >= 1, mode 0 / 1) or Dm alone, kind one of the MDE_F_L_* losses, d_scale positive and finite, "
                   "0 <= slices <= %d, 1 <= n_rows <= n_q and n_rows == n_q without rows, non-null XQ / XC / outputs / "
-                  "work)", PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+                  "work)", fn, PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
     return MDE_E_INVALID;
   }
+  if (!pair_weights_ok(fn, wsrc, p, W, false, 0.0)) return MDE_E_INVALID;
   const int64_t s = cross_resolve_slices(n_rows, n_c, slices);
   if (s < 0) return (int)s;
   const int64_t part_rows = pair_loss_rows_part_rows(n_q, n_c, slices);
@@ -440,10 +605,171 @@ extern "C" int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, co
   const MdeScalars S = {s0, s1, s2};
   hipStream_t st = mde_stream(stream);
   const int rc = pair_loss_walk<false, true>(n_rows, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s,
-                                             part, rows, st);
+                                             part, rows, wsrc, pair_weights(wsrc, p, W), st);
   if (rc != MDE_OK) return rc;
   hipLaunchKernelGGL(k_pair_loss_fold_rows, dim3(mde_grid(n_rows * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st,
                      n_rows, (int)d, (int)s, (double)n_c, part, rows, row_loss, row_grad);
+  MDE_LAUNCH_CHECK();
+  return MDE_OK;
+}
+
+extern "C" int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                                        int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                                        const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
+                                        int64_t n_rows, const int32_t* rows, double* row_loss, float* row_grad,
+                                        void* work, void* stream) {
+  return pair_loss_rect_rows("mde_pair_loss_cross_rows", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0,
+                             s1, s2, slices, n_rows, rows, PAIR_W_NONE, 0.0f, nullptr, row_loss, row_grad, work,
+                             stream);
+}
+
+// mde_pair_loss_cross_rows with a weight per pair; W [n_q, n_c] is read through the list as Dm is.  The divisor
+// stays n_c (there is no `pairs`): the per-row solver's arithmetic does not change.
+extern "C" int mde_pair_loss_cross_rows_weighted(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                                                 int32_t mode, const float* Dm, float d_scale, int32_t d,
+                                                 const float* XQ, const float* XC, int32_t kind, float s0, float s1,
+                                                 float s2, int32_t slices, int64_t n_rows, const int32_t* rows,
+                                                 int32_t wsource, float p, const float* W, double* row_loss,
+                                                 float* row_grad, void* work, void* stream) {
+  return pair_loss_rect_rows("mde_pair_loss_cross_rows_weighted", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC,
+                             kind, s0, s1, s2, slices, n_rows, rows, wsource, p, W, row_loss, row_grad, work, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// mde_pair_weights_check: what pymde_amd.dense has to know of a weight matrix before the walk may
+// trust it, in ONE pass over W (and over Dm when there is one).  Workgroup (x, y) takes the 64x64 tiles (x, y),
+// (x, y + gridDim.y), ... (at most PAIR_WC_SLICES workgroups share a row block, so a row's kept count costs that many
+// integer atomics, not one per tile): wave w reads the 256-byte segments of the tile rows w, w + 4, ... (lane =
+// column), and,
+// for the square problem, the mirror tiles of W and Dm are staged in LDS first so that W[j][i] is read coalesced too.
+// Integer counters only (ballot + popcount per wave, one integer atomic per wave and counter; the maxima as the bit
+// patterns of non-negative floats, which order as unsigned integers): the results do not depend on the order.
+#define PAIR_WC_COUNTS 5   // non-finite w | negative w | kept pairs | rows without a kept pair | kept with a bad D
+#define PAIR_WC_SLICES 16  // workgroups per row block
+#define PAIR_WC_TOPS 4     // max |W - W^T| | max |W| | max |Dm - Dm^T| over the kept | max Dm over the kept
+
+__device__ __forceinline__ float pair_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+template <bool SQUARE>
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_weights_check(int n_q, int n_c, const float* __restrict__ W,
+                                                                  const float* __restrict__ Dm,
+                                                                  unsigned long long* __restrict__ counts,
+                                                                  unsigned* __restrict__ tops,
+                                                                  int32_t* __restrict__ row_kept) {
+  __shared__ float tW[SQUARE ? PAIR_TILE : 1], tD[SQUARE ? PAIR_TILE : 1];   // the mirror tiles, [col][row]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * KNN_BM;
+  const int64_t tiles_c = ((int64_t)n_c + KNN_BN - 1) / KNN_BN;
+  unsigned long long c_bad = 0, c_neg = 0, c_kept = 0, c_badd = 0;   // the wave's counts: the same in every lane
+  float m_asym = 0.0f, m_top = 0.0f, md_asym = 0.0f, md_top = 0.0f;
+  int row_count[KNN_BM / 4];                                         // of the wave's rows w, w + 4, ...; likewise
+#pragma unroll
+  for (int q = 0; q < KNN_BM / 4; ++q) row_count[q] = 0;
+  auto finite = [](float v) { return fabsf(v) <= PAIR_FLT_MAX; };
+  for (int64_t ct = blockIdx.y; ct < tiles_c; ct += gridDim.y) {
+    const int64_t col0 = ct * KNN_BN;
+    if constexpr (SQUARE) {
+      __syncthreads();                                          // the last tile's mirrors have been read
+      const int64_t gc = row0 + lane < n_c ? row0 + lane : n_c - 1;
+#pragma unroll
+      for (int q = 0; q < KNN_BM / 4; ++q) {
+        const int64_t gr = col0 + w + 4 * q < n_q ? col0 + w + 4 * q : n_q - 1;
+        tW[(w + 4 * q) * (KNN_BN + 1) + lane] = W[gr * (int64_t)n_c + gc];
+        if (Dm) tD[(w + 4 * q) * (KNN_BN + 1) + lane] = Dm[gr * (int64_t)n_c + gc];
+      }
+      __syncthreads();
+    }
+    const int64_t j = col0 + lane, gc = j < n_c ? j : n_c - 1;
+#pragma unroll
+    for (int q = 0; q < KNN_BM / 4; ++q) {
+      const int rr = w + 4 * q;
+      const int64_t i = row0 + rr, gr = i < n_q ? i : n_q - 1;
+      const bool in = i < n_q && j < n_c && (!SQUARE || i != j);     // the diagonal of a square W is ignored
+      const float a = W[gr * (int64_t)n_c + gc];
+      const bool fin = finite(a), kept = in && a > 0.0f;
+      c_bad += __popcll(__ballot(in && !fin));
+      c_neg += __popcll(__ballot(in && a < 0.0f));
+      c_kept += __popcll(__ballot(kept && (!SQUARE || i < j)));
+      row_count[q] += __popcll(__ballot(kept));
+      if constexpr (SQUARE) {
+        const float diff = fabsf(a - tW[lane * (KNN_BN + 1) + rr]);
+        if (in && fin) m_top = fmaxf(m_top, fabsf(a));
+        if (in && fin && finite(diff)) m_asym = fmaxf(m_asym, diff);
+      }
+      if (Dm) {
+        const float dv = Dm[gr * (int64_t)n_c + gc];
+        const bool d_ok = dv >= 0.0f && finite(dv);
+        c_badd += __popcll(__ballot(kept && !d_ok));
+        if constexpr (SQUARE) {
+          const float diff = fabsf(dv - tD[lane * (KNN_BN + 1) + rr]);
+          if (kept && d_ok) md_top = fmaxf(md_top, dv);
+          if (kept && d_ok && finite(diff)) md_asym = fmaxf(md_asym, diff);
+        }
+      }
+    }
+  }
+  m_asym = pair_wave_max(m_asym), m_top = pair_wave_max(m_top);
+  md_asym = pair_wave_max(md_asym), md_top = pair_wave_max(md_top);
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < KNN_BM / 4; ++q)
+      if (row_count[q] > 0) atomicAdd(&row_kept[row0 + w + 4 * q], row_count[q]);   // (kept implies a row of W)
+    if (c_bad) atomicAdd(&counts[0], c_bad);
+    if (c_neg) atomicAdd(&counts[1], c_neg);
+    if (c_kept) atomicAdd(&counts[2], c_kept);
+    if (c_badd) atomicAdd(&counts[4], c_badd);
+    if (SQUARE) {
+      atomicMax(&tops[0], __float_as_uint(m_asym));
+      atomicMax(&tops[1], __float_as_uint(m_top));
+      atomicMax(&tops[2], __float_as_uint(md_asym));
+      atomicMax(&tops[3], __float_as_uint(md_top));
+    }
+  }
+}
+
+// counts[3] = the number of rows whose kept count is zero
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_weights_empty_rows(int64_t n_q,
+                                                                       const int32_t* __restrict__ row_kept,
+                                                                       unsigned long long* __restrict__ counts) {
+  unsigned long long c = 0;
+  // (whole waves: every lane of a wave runs the same number of rounds, so the ballot sees all of them)
+  for (int64_t i0 = (int64_t)blockIdx.x * MDE_BLOCK; i0 < n_q; i0 += (int64_t)gridDim.x * MDE_BLOCK) {
+    const int64_t i = i0 + threadIdx.x;
+    c += __popcll(__ballot(i < n_q && row_kept[i < n_q ? i : n_q - 1] == 0));
+  }
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&counts[3], c);
+}
+
+extern "C" int mde_pair_weights_check(int64_t n_q, int64_t n_c, int32_t square, const float* W, const float* Dm,
+                                      int64_t* counts, float* tops, int32_t* row_kept, void* stream) {
+  if (n_q < 1 || n_q >= ((int64_t)1 << 31) || n_c < 1 || n_c >= ((int64_t)1 << 31) || (square != 0 && square != 1) ||
+      (square && n_q != n_c) || !W || !counts || !tops || !row_kept) {
+    mde_set_error("mde_pair_weights_check: invalid arguments (1 <= n_q, n_c < 2^31, square 0 or 1 and then n_q == n_c, "
+                  "non-null W / counts / tops / row_kept)");
+    return MDE_E_INVALID;
+  }
+  hipStream_t st = mde_stream(stream);
+  MDE_HIP(hipMemsetAsync(counts, 0, PAIR_WC_COUNTS * sizeof(int64_t), st));
+  MDE_HIP(hipMemsetAsync(tops, 0, PAIR_WC_TOPS * sizeof(float), st));
+  MDE_HIP(hipMemsetAsync(row_kept, 0, (size_t)n_q * sizeof(int32_t), st));
+  const int64_t tiles_c = (n_c + KNN_BN - 1) / KNN_BN;
+  const dim3 grid((unsigned)((n_q + KNN_BM - 1) / KNN_BM),
+                  (unsigned)(tiles_c < PAIR_WC_SLICES ? tiles_c : PAIR_WC_SLICES));
+  unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
+  unsigned* t = reinterpret_cast<unsigned*>(tops);
+  if (square)
+    hipLaunchKernelGGL(k_pair_weights_check<true>, grid, dim3(MDE_BLOCK), 0, st, (int)n_q, (int)n_c, W, Dm, c, t,
+                       row_kept);
+  else
+    hipLaunchKernelGGL(k_pair_weights_check<false>, grid, dim3(MDE_BLOCK), 0, st, (int)n_q, (int)n_c, W, Dm, c, t,
+                       row_kept);
+  MDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pair_weights_empty_rows, dim3(mde_grid(n_q, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_q,
+                     row_kept, c);
   MDE_LAUNCH_CHECK();
   return MDE_OK;
 }

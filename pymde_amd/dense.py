@@ -15,14 +15,21 @@ The solver is the one ``MDE.embed`` calls (``optim.lbfgs``), on its generic path
 embedded row) pair with the embedded rows held fixed, which places new rows into a finished distance-preserving
 embedding.  ``LandmarkMDE`` (``preserve_distances(landmarks=m)``) is landmark MDS on the two: a ``DenseMDE`` of m
 landmark rows, then a ``DensePlacement`` of all the others against them.
+
+``weights=`` gives every pair a weight: a number ``p`` weighs by ``D^-p`` (``Quadratic`` with
+``weights=1`` is Sammon mapping), a matrix weighs pair by pair, and a zero in it is a MISSING pair -- an incomplete
+dissimilarity matrix, or the pairs of a ``Graph`` that no path joins (``DenseMDE.from_graph``).
 """
 import collections
 import math
+import numbers
 
+import numpy as np
 import torch
 
 from pymde_amd import _lib
 from pymde_amd import constraints
+from pymde_amd import graph as _graph
 from pymde_amd import metrics as _metrics
 from pymde_amd import optim
 from pymde_amd import preprocess
@@ -37,6 +44,92 @@ MAX_DIM = 8            # PAIR_LOSS_MAX_D of csrc/mde_pair_loss.hip
 MAX_SLICES = 65535     # CROSS_MAX_SLICES of csrc/mde_knn_slices.h
 SYMMETRY_RTOL = 1e-5   # |D - D^T| may reach this fraction of the largest entry (a float32 product of two roundings)
 _FIRST_LOSS = _function.KIND["L_QUADRATIC"]
+W_NONE, W_POWER, W_MATRIX = 0, 1, 2   # MDE_PAIR_W_* of include/mde_hip.h
+
+Weights = collections.namedtuple("Weights", ["source", "p", "W"])
+Weights.__doc__ = """The ``weights=`` of a dense problem as the kernels take it: ``source`` (MDE_PAIR_W_*), the exponent
+``p`` of the power form, and ``W``, the matrix of the matrix form (as it was passed, until the problem puts it on its
+device as float32)."""
+NO_WEIGHTS = Weights(W_NONE, 0.0, None)
+
+WeightStats = collections.namedtuple("WeightStats", ["nonfinite", "negative", "kept", "empty_rows", "bad_deviations",
+                                                     "asymmetry", "largest", "deviation_asymmetry",
+                                                     "largest_deviation", "row_kept"])
+WeightStats.__doc__ = """What ``mde_pair_weights_check`` reports of a weight matrix (and the deviations it weighs)."""
+
+
+def parse_weights(weights, shape=None, allow_matrix=True):
+    """The ``Weights`` of a ``weights=`` argument; needs no GPU.  ``None``: no weights.  A real number ``p`` (not a
+    bool; finite, ``>= 0``): the power form ``w = D^-p``.  A two-dimensional numpy array or torch tensor (bool,
+    integer or floating point): the matrix form, which must have the shape ``shape``.  ``ValueError`` otherwise, and
+    for a matrix where ``allow_matrix`` is false."""
+    if weights is None:
+        return NO_WEIGHTS
+    accepted = ("`weights` is None, a real number p >= 0 (every pair is weighed by D^-p), or a matrix of non-negative "
+                "weights with one entry per pair (0: the pair is missing)")
+    if isinstance(weights, (bool, np.bool_, str, bytes)):
+        raise ValueError(f"`weights` is {weights!r}; {accepted}")
+    if isinstance(weights, numbers.Real) or (isinstance(weights, (np.ndarray, torch.Tensor)) and weights.ndim == 0
+                                             and weights.dtype not in (torch.bool, np.bool_)):
+        p = float(weights)
+        if not (math.isfinite(p) and p >= 0.0):
+            raise ValueError(f"the exponent `weights`={weights!r} must be finite and >= 0; {accepted}")
+        return Weights(W_POWER, p, None)
+    if not isinstance(weights, (np.ndarray, torch.Tensor)):
+        raise ValueError(f"`weights` is a {type(weights).__name__}; {accepted}, as a numpy array or a torch tensor")
+    if not allow_matrix:
+        raise ValueError("a weight matrix is not supported here: landmark MDS draws its rows itself, so only the "
+                         "power form `weights=p` can be handed to both of its stages")
+    if isinstance(weights, torch.Tensor):
+        ok = not weights.is_complex() and weights.layout == torch.strided
+    else:
+        ok = weights.dtype.kind in "biuf"
+    if not ok:
+        raise ValueError(f"`weights` has dtype {weights.dtype}; {accepted}")
+    if weights.ndim != 2 or (shape is not None and tuple(int(v) for v in weights.shape) != tuple(shape)):
+        raise ValueError(f"a `weights` matrix must have one entry per pair, shape {tuple(shape) if shape else '[., .]'}"
+                         f"; got shape {tuple(weights.shape)}")
+    return Weights(W_MATRIX, 0.0, weights)
+
+
+def weight_stats(W, Dm=None, square=True):
+    """``mde_pair_weights_check`` on a float32 ``W`` on one GPU (and the float32 ``Dm`` of the same shape it weighs):
+    a ``WeightStats``; one launch sequence and one read-back, ``row_kept`` (int32) stays on the device."""
+    n_q, n_c, device = int(W.shape[0]), int(W.shape[1]), W.device
+    counts = torch.empty(5, dtype=torch.int64, device=device)
+    tops = torch.empty(4, dtype=torch.float32, device=device)
+    row_kept = torch.empty(n_q, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().mde_pair_weights_check(n_q, n_c, 1 if square else 0, _lib.ptr(W), _lib.ptr(Dm),
+                                                      _lib.ptr(counts), _lib.ptr(tops), _lib.ptr(row_kept),
+                                                      _lib.stream_ptr(device)))
+    c, t = counts.tolist(), tops.tolist()
+    return WeightStats(c[0], c[1], c[2], c[3], c[4], t[0], t[1], t[2], t[3], row_kept)
+
+
+def _device_weights(weights, Dm, square, device):
+    """The matrix form on the device, checked: ``(Weights with W float32 on `device`, WeightStats)``; ``ValueError``
+    saying which rule the matrix (or a deviation it keeps) breaks."""
+    W = torch.as_tensor(weights.W).to(device=device, dtype=torch.float32).contiguous()
+    stats = weight_stats(W, Dm, square)
+    if stats.nonfinite:
+        raise ValueError(f"`weights` is not finite: {stats.nonfinite} of its entries are NaN or infinite")
+    if stats.negative:
+        raise ValueError(f"`weights` is not non-negative: {stats.negative} of its entries are below zero")
+    if square and stats.asymmetry > SYMMETRY_RTOL * stats.largest:
+        raise ValueError(f"`weights` is not symmetric: an entry differs from its mirror image by "
+                         f"{stats.asymmetry:.3g} (the largest entry is {stats.largest:.3g})")
+    if stats.empty_rows:
+        raise ValueError(f"`weights` leaves {stats.empty_rows} of the {int(W.shape[0])} rows without a pair (every "
+                         "weight of the row is zero): such an item has no position")
+    if stats.bad_deviations:
+        raise ValueError(f"`distance_matrix` is NaN, infinite or negative at {stats.bad_deviations} entries that "
+                         "`weights` keeps (only the pairs of weight zero may be unknown)")
+    if square and stats.deviation_asymmetry > SYMMETRY_RTOL * stats.largest_deviation:
+        raise ValueError(f"`distance_matrix` is not symmetric on the pairs that `weights` keeps: an entry differs "
+                         f"from its mirror image by {stats.deviation_asymmetry:.3g} (the largest kept entry is "
+                         f"{stats.largest_deviation:.3g})")
+    return Weights(W_MATRIX, 0.0, W), stats
 
 LossSpec = collections.namedtuple("LossSpec", ["kind", "scalars", "weighted"])
 LossSpec.__doc__ = """What ``mde_pair_loss`` needs of a loss: its ``kind`` (MDE_F_L_* of include/mde_hip.h), its three
@@ -50,8 +143,8 @@ _ACCEPTED = ("a dense problem takes a loss of pymde_amd.losses as a callable of 
 def loss_spec(loss):
     """The ``LossSpec`` of ``loss``, a callable of the deviations as the recipes take it.  Needs no GPU: the callable
     is tried on ``torch.ones(1)``.  ``ValueError`` (naming what is accepted) for a penalty, for a callable whose
-    result has no ``_hip_spec``, and for weights other than the default ``1 / delta^2``: a dense problem has no
-    per-pair arrays."""
+    result has no ``_hip_spec``, and for weights other than the default ``1 / delta^2``: per-pair weights go to the
+    problem's ``weights=``, not into the loss."""
     if isinstance(loss, torch.nn.Module) or not callable(loss):
         raise ValueError(f"`loss` is {loss!r}, not a callable of the deviations; {_ACCEPTED}")
 
@@ -72,8 +165,8 @@ def loss_spec(loss):
         for value, want in ((1.0, 1.0), (2.0, 0.25)):
             a1 = probe(value)[1].a1
             if not isinstance(a1, torch.Tensor) or a1.numel() != 1 or float(a1.reshape(-1)[0]) != want:
-                raise ValueError(f"{type(f).__name__} was given weights of its own; a dense problem has no per-pair "
-                                 f"arrays and weighs by the default 1 / delta^2; {_ACCEPTED}")
+                raise ValueError(f"{type(f).__name__} was given weights of its own; a dense problem takes a loss with "
+                                 f"the default 1 / delta^2 and its per-pair weights through `weights=`; {_ACCEPTED}")
     return LossSpec(int(spec.kind), tuple(float(s) for s in spec.scalars), weighted)
 
 
@@ -91,9 +184,11 @@ def check_source(data, metric):
     return metric
 
 
-def _pair_loss(X, spec, A=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=None):
+def _pair_loss(X, spec, A=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=None, weights=None, pairs=None):
     """``mde_pair_loss`` on prepared float32 tensors on one GPU: ``(loss float64 [1], grad float32 [n, d], row_loss
-    float64 [n])`` on that GPU.  Exactly one of ``A`` (the prepared data rows) and ``Dm`` (the [n, n] matrix)."""
+    float64 [n])`` on that GPU.  Exactly one of ``A`` (the prepared data rows) and ``Dm`` (the [n, n] matrix).  With
+    ``weights`` (a ``Weights`` whose ``W`` is float32 on that GPU) ``mde_pair_loss_weighted``; ``pairs`` is then the
+    number of pairs that count (default: all)."""
     n, d, device = int(X.shape[0]), int(X.shape[1]), X.device
     lib = _lib.load()
     loss = torch.empty(1, dtype=torch.float64, device=device)
@@ -102,10 +197,14 @@ def _pair_loss(X, spec, A=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=Non
     with torch.cuda.device(device):
         if work is None:
             work = _work(lib, n, d, slices, device)
-        _lib.check(lib.mde_pair_loss(n, 0 if A is None else int(A.shape[1]), _lib.ptr(A), mode, _lib.ptr(Dm),
-                                     float(d_scale), d, _lib.ptr(X), spec.kind, spec.scalars[0], spec.scalars[1],
-                                     spec.scalars[2], slices, _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(row_loss),
-                                     _lib.ptr(work), _lib.stream_ptr(device)))
+        head = (n, 0 if A is None else int(A.shape[1]), _lib.ptr(A), mode, _lib.ptr(Dm), float(d_scale), d,
+                _lib.ptr(X), spec.kind, spec.scalars[0], spec.scalars[1], spec.scalars[2], slices)
+        tail = (_lib.ptr(loss), _lib.ptr(grad), _lib.ptr(row_loss), _lib.ptr(work), _lib.stream_ptr(device))
+        if weights is None:
+            _lib.check(lib.mde_pair_loss(*head, *tail))
+        else:
+            pairs = 0.5 * n * (n - 1) if pairs is None else float(pairs)
+            _lib.check(lib.mde_pair_loss_weighted(*head, weights.source, weights.p, _lib.ptr(weights.W), pairs, *tail))
     return loss, grad, row_loss
 
 
@@ -171,13 +270,23 @@ class DenseMDE(object):
     use their default weights ``1 / D^2``.  ``deviation_scale``: every deviation is multiplied by it (what
     ``preserve_distances`` does for ``Standardized``).  ``1 <= embedding_dim <= 8``.
 
+    ``weights``: ``None``, or a weight per pair.  A real number ``p >= 0`` weighs every pair by
+    ``D^-p`` (``D`` after ``deviation_scale``), formed in the kernel: ``Quadratic`` with ``weights=1`` is Sammon
+    mapping.  A matrix [n, n] (numpy or torch; bool or numeric; kept as float32 on the GPU) gives the weights
+    themselves: it must be finite, non-negative and symmetric (to a relative 1e-5), its diagonal is ignored, and a
+    ZERO marks a missing pair -- the pair takes no part, ``p`` becomes the number of pairs that are kept, the mean is
+    over those, and a ``distance_matrix`` may hold anything (NaN included) there; it is then checked on the kept pairs
+    only.  Every row must keep a pair.  For the weighted losses (``WeightedQuadratic``) the weight replaces the default
+    ``1 / D^2``; every other loss is multiplied by it.  ``DenseMDE.from_graph`` builds such a problem from a
+    ``Graph``'s shortest paths.
+
     After ``embed()``: ``X``, ``solve_stats``, ``value`` and ``residual_norm``, as for ``MDE``.  The per-pair
     ``distances`` / ``distortions`` / ``high_distortion_pairs`` of ``MDE`` are n^2 values and are not provided;
     ``item_distortions`` has one value per item.  With ``Anchored`` the anchor-anchor pairs stay in the mean: they
     add a constant to the value and nothing to the gradient of the free rows."""
 
     def __init__(self, data=None, embedding_dim=2, loss=losses.Absolute, constraint=None, distance_matrix=None,
-                 metric="euclidean", deviation_scale=1.0, device=None):
+                 metric="euclidean", deviation_scale=1.0, device=None, weights=None):
         if (data is None) == (distance_matrix is None):
             raise ValueError("exactly one of `data` and `distance_matrix` must be given")
         embedding_dim = int(embedding_dim)
@@ -198,6 +307,7 @@ class DenseMDE(object):
         n = int(source.shape[0])
         if n < 2:
             raise ValueError("a dense problem needs at least two items")
+        weights = parse_weights(weights, (n, n))
         if device is None:
             device = source.device if isinstance(source, torch.Tensor) and source.is_cuda else util.get_default_device()
         self.device = util.require_cuda_device(device)
@@ -207,10 +317,16 @@ class DenseMDE(object):
             self._mode = quality._pair_modes(metric)[0]
         else:
             self._Dm = torch.as_tensor(distance_matrix).to(device=self.device, dtype=torch.float32).contiguous()
-            _check_distance_matrix(self._Dm)
+            if weights.source != W_MATRIX:
+                _check_distance_matrix(self._Dm)
         self.n_items = n
         self.embedding_dim = embedding_dim
-        self.p = n * (n - 1) // 2
+        self.n_all_pairs = n * (n - 1) // 2
+        self.p = self.n_all_pairs
+        self._weights, self._row_kept = (None if weights.source == W_NONE else weights), None
+        if weights.source == W_MATRIX:
+            self._weights, stats = _device_weights(weights, self._Dm, True, self.device)
+            self.p, self._row_kept = int(stats.kept), stats.row_kept
         self.metric = metric if data is not None else None
         self.deviation_scale = deviation_scale
         self.loss = loss
@@ -224,8 +340,21 @@ class DenseMDE(object):
     def __str__(self):
         source = "data matrix, metric %s" % self.metric if self._A is not None else "distance matrix"
         return ("Dense MDE problem:\n\tn (number of items) {0}\n\tm (embedding dimension) {1}\n"
-                "\tp (number of pairs, all of them) {2}\n\tdeviations from a {3}\n\tconstraint {4}\n\tdevice {5}".format(
-                    self.n_items, self.embedding_dim, self.p, source, self.constraint.name(), self.device))
+                "\tp (number of pairs, {2}) {3}\n\tdeviations from a {4}{5}\n\tconstraint {6}\n\tdevice {7}".format(
+                    self.n_items, self.embedding_dim, self._pairs_note(), self.p, source, self._weights_note(),
+                    self.constraint.name(), self.device))
+
+    def _pairs_note(self):
+        if self._row_kept is None:
+            return "all of them"
+        return "those of non-zero weight, of %d" % self.n_all_pairs
+
+    def _weights_note(self):
+        if self._weights is None:
+            return ""
+        if self._weights.source == W_POWER:
+            return "\n\tweights D^-%g" % self._weights.p
+        return "\n\tweights from a matrix"
 
     # ------------------------------------------------------------------ plumbing
     def _embedding_arg(self, X):
@@ -253,7 +382,7 @@ class DenseMDE(object):
             with torch.cuda.device(self.device):
                 self._work_buffer = _work(_lib.load(), self.n_items, self.embedding_dim, 0, self.device)
         return _pair_loss(X.contiguous(), self._spec, A=self._A, mode=self._mode, Dm=self._Dm,
-                          d_scale=self.deviation_scale, work=self._work_buffer)
+                          d_scale=self.deviation_scale, work=self._work_buffer, weights=self._weights, pairs=self.p)
 
     # ------------------------------------------------------------------ evaluators
     def average_distortion(self, X=None):
@@ -262,9 +391,33 @@ class DenseMDE(object):
 
     def item_distortions(self, X=None):
         """float32 [n]: for every item the mean of the loss over its ``n - 1`` pairs (colour a plot by it).  Their
-        mean is the average distortion."""
+        mean is the average distortion.  With a weight matrix: over the pairs the item keeps (their mean, weighted
+        by those counts, is then the average distortion)."""
         row_loss = self._evaluate(self._embedding_arg(X).detach())[2]
+        if self._row_kept is not None:
+            return (row_loss / self._row_kept.to(torch.float64)).to(torch.float32)
         return (row_loss / float(self.n_items - 1)).to(torch.float32)
+
+    @classmethod
+    def from_graph(cls, graph, embedding_dim=2, loss=losses.Absolute, constraint=None, max_length=None):
+        """The dense problem over the pairs of nodes of a ``Graph`` that a path joins: the deviations are the
+        shortest-path lengths (``graph.shortest_paths``, all of them), scattered into a float32 [n, n] matrix, and
+        the weight matrix is 1 where a path exists (of length at most ``max_length``, if given) and 0 where none
+        does -- pairs in different components are missing, not infinitely far.  A node that reaches no other is a
+        ``ValueError`` (a row without a pair).  O(n^2) memory: two float32 matrices."""
+        if not isinstance(graph, _graph.Graph):
+            raise ValueError("`graph` must be a pymde_amd.Graph instance.")
+        paths = _graph.shortest_paths(graph, max_length=max_length)
+        n, device = int(graph.n_items), paths.edges.device
+        D = torch.zeros((n, n), dtype=torch.float32, device=device)
+        W = torch.zeros((n, n), dtype=torch.float32, device=device)
+        i, j = paths.edges[:, 0], paths.edges[:, 1]
+        D[i, j] = paths.distances
+        D[j, i] = paths.distances
+        W[i, j] = 1.0
+        W[j, i] = 1.0
+        return cls(distance_matrix=D, embedding_dim=embedding_dim, loss=loss, constraint=constraint, device=device,
+                   weights=W)
 
     # ------------------------------------------------------------------ the solve
     def embed(self, X=None, eps=1e-5, max_iter=300, memory_size=10, verbose=False, print_every=None,
@@ -313,10 +466,12 @@ class DenseMDE(object):
 
 
 # ---------------------------------------------------------------------- the rectangular problem
-def _pair_loss_cross(XQ, XC, spec, Q=None, C=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=None):
+def _pair_loss_cross(XQ, XC, spec, Q=None, C=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=None, weights=None,
+                     pairs=None):
     """``mde_pair_loss_cross`` on prepared float32 tensors on one GPU: ``(loss float64 [1], grad float32 [n_q, d],
     row_loss float64 [n_q])`` on that GPU.  Either both ``Q`` and ``C`` (the prepared data rows of the free and of
-    the fixed items) or ``Dm`` (the [n_q, n_c] matrix)."""
+    the fixed items) or ``Dm`` (the [n_q, n_c] matrix).  With ``weights`` (a ``Weights``; ``W`` [n_q, n_c] float32 on
+    that GPU) ``mde_pair_loss_cross_weighted``; ``pairs`` is then the number of pairs that count (default: all)."""
     n_q, n_c, d, device = int(XQ.shape[0]), int(XC.shape[0]), int(XQ.shape[1]), XQ.device
     lib = _lib.load()
     loss = torch.empty(1, dtype=torch.float64, device=device)
@@ -325,11 +480,16 @@ def _pair_loss_cross(XQ, XC, spec, Q=None, C=None, mode=0, Dm=None, d_scale=1.0,
     with torch.cuda.device(device):
         if work is None:
             work = _work_cross(lib, n_q, n_c, d, slices, device)
-        _lib.check(lib.mde_pair_loss_cross(n_q, n_c, 0 if Q is None else int(Q.shape[1]), _lib.ptr(Q), _lib.ptr(C),
-                                           mode, _lib.ptr(Dm), float(d_scale), d, _lib.ptr(XQ), _lib.ptr(XC),
-                                           spec.kind, spec.scalars[0], spec.scalars[1], spec.scalars[2], slices,
-                                           _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(row_loss), _lib.ptr(work),
-                                           _lib.stream_ptr(device)))
+        head = (n_q, n_c, 0 if Q is None else int(Q.shape[1]), _lib.ptr(Q), _lib.ptr(C), mode, _lib.ptr(Dm),
+                float(d_scale), d, _lib.ptr(XQ), _lib.ptr(XC), spec.kind, spec.scalars[0], spec.scalars[1],
+                spec.scalars[2], slices)
+        tail = (_lib.ptr(loss), _lib.ptr(grad), _lib.ptr(row_loss), _lib.ptr(work), _lib.stream_ptr(device))
+        if weights is None:
+            _lib.check(lib.mde_pair_loss_cross(*head, *tail))
+        else:
+            pairs = float(n_q) * n_c if pairs is None else float(pairs)
+            _lib.check(lib.mde_pair_loss_cross_weighted(*head, weights.source, weights.p, _lib.ptr(weights.W), pairs,
+                                                        *tail))
     return loss, grad, row_loss
 
 
@@ -393,7 +553,8 @@ class DensePlacement(DenseMDE):
 
     ``X`` [n_old, d] is the embedding of the old rows; it is used as float32 and never modified, and ``d`` (1 .. 8)
     is taken from it.  ``loss`` and ``deviation_scale`` as for ``DenseMDE``.  A new row identical to an old one in
-    both spaces is an ordinary pair (D = E = 0).
+    both spaces is an ordinary pair (D = E = 0).  ``DensePlacement.weighted(..., weights=)`` builds the same problem
+    with a weight per pair, or with missing pairs.
 
     ``embed()`` starts, by default, every new row at the mean of the embedding vectors of its ``d + 1`` nearest old
     rows (``d + 1`` points fix a position in R^d; perturbed by 1e-4 if a new row lands exactly on an old one).  The
@@ -408,6 +569,21 @@ class DensePlacement(DenseMDE):
 
     def __init__(self, data, X, new_data, loss=losses.Absolute, metric="euclidean", deviation_scale=1.0,
                  distance_matrix=None, device=None):
+        self._setup(data, X, new_data, loss, metric, deviation_scale, distance_matrix, device, None)
+
+    @classmethod
+    def weighted(cls, data, X, new_data, *, weights, loss=losses.Absolute, metric="euclidean", deviation_scale=1.0,
+                 distance_matrix=None, device=None):
+        """The placement with a weight per (new row, embedded row) pair: the arguments of the constructor and
+        ``weights``, as for ``DenseMDE`` -- ``None``, a number ``p`` (every pair is weighed by ``D^-p``), or a matrix
+        [n_new, n_old] (no symmetry to ask for) whose zeros are MISSING pairs.  Every new row must keep a pair; ``p``
+        is the number kept; a ``distance_matrix`` is then checked on its kept pairs only; with ``solver="rows"`` the
+        reported values are those of this joint problem.  (The constructor's own parameter list is fixed.)"""
+        self = cls.__new__(cls)
+        self._setup(data, X, new_data, loss, metric, deviation_scale, distance_matrix, device, weights)
+        return self
+
+    def _setup(self, data, X, new_data, loss, metric, deviation_scale, distance_matrix, device, weights):
         from_data = data is not None or new_data is not None
         if from_data == (distance_matrix is not None):
             raise ValueError("exactly one source of the deviations must be given: `data` and `new_data`, or "
@@ -448,6 +624,7 @@ class DensePlacement(DenseMDE):
         if n_new < 1:
             raise ValueError("`new_data` needs at least one row" if from_data else
                              "`distance_matrix` needs at least one row")
+        weights = parse_weights(weights, (n_new, n_old))
         if device is None:
             on_gpu = [t.device for t in (X, data, new_data, distance_matrix)
                       if isinstance(t, torch.Tensor) and t.is_cuda]
@@ -470,11 +647,17 @@ class DensePlacement(DenseMDE):
             self._mode = quality._pair_modes(metric)[0]
         else:
             self._Dm = torch.as_tensor(distance_matrix).to(device=self.device, dtype=torch.float32).contiguous()
-            _check_rectangular_matrix(self._Dm)
+            if weights.source != W_MATRIX:
+                _check_rectangular_matrix(self._Dm)
         self.n_items = n_new
         self.n_old = n_old
         self.embedding_dim = embedding_dim
-        self.p = n_new * n_old
+        self.n_all_pairs = n_new * n_old
+        self.p = self.n_all_pairs
+        self._weights, self._row_kept = (None if weights.source == W_NONE else weights), None
+        if weights.source == W_MATRIX:
+            self._weights, stats = _device_weights(weights, self._Dm, False, self.device)
+            self.p, self._row_kept = int(stats.kept), stats.row_kept
         self.metric = metric if from_data else None
         self.deviation_scale = deviation_scale
         self.loss = loss
@@ -490,9 +673,11 @@ class DensePlacement(DenseMDE):
     def __str__(self):
         source = "data matrices, metric %s" % self.metric if self._A is not None else "distance matrix"
         return ("Dense placement problem:\n\tn (number of new items) {0}\n\tembedded items, held fixed {1}\n"
-                "\tm (embedding dimension) {2}\n\tp (number of pairs, new against embedded) {3}\n"
-                "\tdeviations from {4}\n\tdevice {5}".format(self.n_items, self.n_old, self.embedding_dim, self.p,
-                                                              source, self.device))
+                "\tm (embedding dimension) {2}\n\tp (number of pairs, new against embedded{3}) {4}\n"
+                "\tdeviations from {5}{6}\n\tdevice {7}".format(
+                    self.n_items, self.n_old, self.embedding_dim,
+                    "" if self._row_kept is None else ": " + self._pairs_note(), self.p, source,
+                    self._weights_note(), self.device))
 
     def _evaluate(self, X):
         """(loss float64 [1], grad float32 [n_new, d], row_loss float64 [n_new]) at a float32 X on the device."""
@@ -501,7 +686,8 @@ class DensePlacement(DenseMDE):
                 self._work_buffer = _work_cross(_lib.load(), self.n_items, self.n_old, self.embedding_dim, 0,
                                                 self.device)
         return _pair_loss_cross(X.contiguous(), self._X_old, self._spec, Q=self._Q, C=self._A, mode=self._mode,
-                                Dm=self._Dm, d_scale=self.deviation_scale, work=self._work_buffer)
+                                Dm=self._Dm, d_scale=self.deviation_scale, work=self._work_buffer,
+                                weights=self._weights, pairs=self.p)
 
     def average_distortion(self, X=None):
         """The average distortion of the new rows ``X`` [n_new, d] over all ``n_new * n_old`` pairs with the embedded
@@ -509,9 +695,11 @@ class DensePlacement(DenseMDE):
         return _DenseDistortion.apply(self._embedding_arg(X), self)
 
     def item_distortions(self, X=None):
-        """float32 [n_new]: for every new row the mean of the loss over its ``n_old`` pairs.  Their mean is the
-        average distortion."""
+        """float32 [n_new]: for every new row the mean of the loss over its ``n_old`` pairs (with a weight matrix:
+        over the pairs it keeps).  Their mean is the average distortion."""
         row_loss = self._evaluate(self._embedding_arg(X).detach())[2]
+        if self._row_kept is not None:
+            return (row_loss / self._row_kept.to(torch.float64)).to(torch.float32)
         return (row_loss / float(self.n_old)).to(torch.float32)
 
     def initialization(self):
@@ -519,7 +707,11 @@ class DensePlacement(DenseMDE):
         embedded rows (fewer when there are fewer), perturbed by 1e-4 if a new row lands exactly on one of
         them."""
         k = min(self.embedding_dim + 1, self.n_old)
-        if self._Dm is not None:
+        if self._Dm is not None and self._row_kept is not None:
+            # (a missing pair's entry may be anything: it is never among the nearest)
+            known = torch.where(self._weights.W > 0, self._Dm, torch.full_like(self._Dm, float("inf")))
+            idx = torch.topk(known, k, dim=1, largest=False).indices
+        elif self._Dm is not None:
             idx = torch.topk(self._Dm, k, dim=1, largest=False).indices
         else:
             # (the prepared rows: translating both by one vector, or normalising each, is idempotent)
@@ -538,7 +730,8 @@ class DensePlacement(DenseMDE):
                                                                self.embedding_dim, 0, self.device)
         return _rows.pair_loss_cross_rows(X.contiguous(), self._X_old, self._spec, row_loss, row_grad, rows=rows,
                                           Q=self._Q, C=self._A, mode=self._mode, Dm=self._Dm,
-                                          d_scale=self.deviation_scale, work=self._rows_work_buffer)
+                                          d_scale=self.deviation_scale, work=self._rows_work_buffer,
+                                          weights=self._weights)
 
     def embed(self, X=None, eps=1e-5, max_iter=300, memory_size=10, verbose=False, print_every=None,
               snapshot_every=None, solver="joint"):
@@ -558,9 +751,10 @@ class DensePlacement(DenseMDE):
         if verbose:
             _problem.LOGGER.info(f"Placing {self.n_items} rows in R^{self.embedding_dim} against {self.n_old} "
                                  f"embedded rows, each row on its own: eps={eps:.1e}, max_iter={max_iter}")
+        # (the rows divide by n_old; n_new n_old / p turns their mean into the mean over the pairs that count)
         result = _rows.solve(self._evaluate_rows, X, self.n_old, eps=eps, max_iter=max_iter,
                              snapshot_every=snapshot_every, verbose=verbose, print_every=print_every,
-                             logger=_problem.LOGGER)
+                             logger=_problem.LOGGER, scale=float(self.n_all_pairs) / float(self.p))
         self.X, self.solve_stats, self.row_status = result.X, result.solve_stats, result.row_status
         self.value, self.residual_norm = result.value, result.residual_norm
         if verbose:
@@ -614,14 +808,16 @@ class LandmarkMDE(object):
 
     ``data``, ``embedding_dim``, ``loss``, ``metric`` as for ``DenseMDE``; ``constraint`` is ``None`` or
     ``Centered()``: the result is centred, and the placed rows can keep no other constraint.  ``seed`` draws the
-    landmarks (``quality._sample_rows``): the same seed gives the same ``landmarks``.
+    landmarks (``quality._sample_rows``): the same seed gives the same ``landmarks``.  ``weights``: ``None`` or a
+    number ``p``, the power form ``D^-p`` of ``DenseMDE``, handed to both stages; a matrix is a ``ValueError``.
 
     After ``embed()``: ``X`` [n, d] in the row order of ``data``, ``landmarks`` (int64 indices), ``landmark_problem``
     (the ``DenseMDE``), ``placement`` (the ``DensePlacement``), ``value`` (the placement's value) and ``solve_stats``
     (a ``LandmarkSolveStats`` of both stages).  Score the result with ``quality.stress(data, X, sample=...)``."""
 
     def __init__(self, data, landmarks, embedding_dim=2, loss=losses.Absolute, constraint=None, metric="euclidean",
-                 seed=None, device=None):
+                 seed=None, device=None, weights=None):
+        parse_weights(weights, allow_matrix=False)
         metric = check_source(data, metric)
         quality._check_matrix(data, "data")
         n = int(data.shape[0])
@@ -636,6 +832,7 @@ class LandmarkMDE(object):
         self.embedding_dim = embedding_dim
         self.metric = metric
         self.loss = loss
+        self.weights = weights
         self.landmarks = quality._sample_rows(n, m, seed).to(torch.int64)
         placed = torch.ones(n, dtype=torch.bool)
         placed[self.landmarks] = False
@@ -643,7 +840,8 @@ class LandmarkMDE(object):
         self._data = data
         self._landmark_data = _take_rows(data, self.landmarks)
         self.landmark_problem = DenseMDE(self._landmark_data, embedding_dim=embedding_dim, loss=loss,
-                                         constraint=constraints.Centered(), metric=metric, device=device)
+                                         constraint=constraints.Centered(), metric=metric, device=device,
+                                         weights=weights)
         self.device = self.landmark_problem.device
         self.placement = None
         self.X = None
@@ -664,8 +862,9 @@ class LandmarkMDE(object):
             X = X.detach().to(device=self.device, dtype=torch.float32)
             start_l, start_p = X[self.landmarks.to(self.device)], X[self.placed.to(self.device)]
         X_l = self.landmark_problem.embed(start_l, **solver_args)
-        self.placement = DensePlacement(self._landmark_data, X_l, _take_rows(self._data, self.placed),
-                                        loss=self.loss, metric=self.metric, device=self.device)
+        self.placement = DensePlacement.weighted(self._landmark_data, X_l, _take_rows(self._data, self.placed),
+                                                 loss=self.loss, metric=self.metric, device=self.device,
+                                                 weights=self.weights)
         X_p = self.placement.embed(start_p, solver=placement_solver, **solver_args)
         out = torch.empty((self.n_items, self.embedding_dim), dtype=torch.float32, device=self.device)
         out[self.landmarks.to(self.device)] = X_l

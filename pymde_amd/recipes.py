@@ -136,7 +136,7 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
                        max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False,
-                       landmarks=None):
+                       landmarks=None, weights=None):
     """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
@@ -160,12 +160,22 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     of O(n^2), which is how all-pairs distance preservation reaches a million rows.  ``constraint`` must be
     ``None`` or ``Centered()``: the placed rows are unconstrained, so ``Standardized`` and ``Anchored`` are a
     ``ValueError``.  ``max_distances`` is not consulted.  Score the result with
-    ``quality.stress(data, X, sample=...)``."""
+    ``quality.stress(data, X, sample=...)``.
+
+    ``weights=p`` (with ``dense=True`` or ``landmarks=m`` only): a real number ``p >= 0``; every pair is weighed by
+    ``D^-p`` as ``DenseMDE(weights=p)`` does it (``loss=Quadratic, weights=1`` is Sammon mapping), in both stages of
+    the landmark path.  A weight matrix is a ``ValueError`` here: build the ``DenseMDE`` directly.  The edge-list
+    path takes its weights through the loss (``WeightedQuadratic``)."""
+    if weights is not None:
+        _dense.parse_weights(weights, allow_matrix=False)
+        if landmarks is None and not dense:
+            raise ValueError("`weights` applies to the dense problems (dense=True or landmarks=m); the edge-list "
+                             "problem is weighed through its loss, e.g. losses.WeightedQuadratic")
     if landmarks is not None:
         return _dense.LandmarkMDE(data, landmarks, embedding_dim=embedding_dim, loss=loss, constraint=constraint,
-                                  metric=metric, seed=seed, device=device)
+                                  metric=metric, seed=seed, device=device, weights=weights)
     if dense:
-        return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric)
+        return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights)
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
     if is_graph:
@@ -196,7 +206,7 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
                        device=edges.device)
 
 
-def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric):
+def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights=None):
     """``preserve_distances(dense=True)``: the ``DenseMDE`` over every pair of the rows of ``data``."""
     metric = _dense.check_source(data, metric)
     if not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
@@ -215,7 +225,7 @@ def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, ver
         rms = (moments.sum_dd / moments.count) ** 0.5
         deviation_scale = float(constraint.natural_length(n_items, embedding_dim)) / rms
     return _dense.DenseMDE(data, embedding_dim=embedding_dim, loss=loss, constraint=constraint, metric=metric,
-                           deviation_scale=deviation_scale, device=device)
+                           deviation_scale=deviation_scale, device=device, weights=weights)
 
 
 def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p,

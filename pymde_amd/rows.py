@@ -44,20 +44,26 @@ def work_cross_rows(lib, n_q, n_c, d, slices, device):
 
 
 def pair_loss_cross_rows(XQ, XC, spec, row_loss, row_grad, rows=None, Q=None, C=None, mode=0, Dm=None, d_scale=1.0,
-                         slices=0, work=None):
+                         slices=0, work=None, weights=None):
     """``mde_pair_loss_cross_rows`` on prepared float32 tensors on one GPU: writes ``row_loss`` (float64 [n_q]) and
-    ``row_grad`` (float32 [n_q, d]) at the rows of ``rows`` (int32, distinct; ``None``: all rows) and nowhere else."""
+    ``row_grad`` (float32 [n_q, d]) at the rows of ``rows`` (int32, distinct; ``None``: all rows) and nowhere else.
+    With ``weights`` (a ``dense.Weights``; ``W`` [n_q, n_c] float32 on that GPU) ``mde_pair_loss_cross_rows_weighted``:
+    the same sums with a weight per pair, still divided by ``n_c``."""
     n_q, n_c, d, device = int(XQ.shape[0]), int(XC.shape[0]), int(XQ.shape[1]), XQ.device
     lib = _lib.load()
     n_rows = n_q if rows is None else int(rows.shape[0])
     with torch.cuda.device(device):
         if work is None:
             work = work_cross_rows(lib, n_q, n_c, d, slices, device)
-        _lib.check(lib.mde_pair_loss_cross_rows(
-            n_q, n_c, 0 if Q is None else int(Q.shape[1]), _lib.ptr(Q), _lib.ptr(C), mode, _lib.ptr(Dm),
-            float(d_scale), d, _lib.ptr(XQ), _lib.ptr(XC), spec.kind, spec.scalars[0], spec.scalars[1],
-            spec.scalars[2], slices, n_rows, _lib.ptr(rows), _lib.ptr(row_loss), _lib.ptr(row_grad), _lib.ptr(work),
-            _lib.stream_ptr(device)))
+        head = (n_q, n_c, 0 if Q is None else int(Q.shape[1]), _lib.ptr(Q), _lib.ptr(C), mode, _lib.ptr(Dm),
+                float(d_scale), d, _lib.ptr(XQ), _lib.ptr(XC), spec.kind, spec.scalars[0], spec.scalars[1],
+                spec.scalars[2], slices, n_rows, _lib.ptr(rows))
+        tail = (_lib.ptr(row_loss), _lib.ptr(row_grad), _lib.ptr(work), _lib.stream_ptr(device))
+        if weights is None:
+            _lib.check(lib.mde_pair_loss_cross_rows(*head, *tail))
+        else:
+            _lib.check(lib.mde_pair_loss_cross_rows_weighted(*head, weights.source, weights.p, _lib.ptr(weights.W),
+                                                             *tail))
     return row_loss, row_grad
 
 
@@ -97,7 +103,7 @@ class RowState(object):
 
 
 def solve(evaluate, X, n_c, eps=1e-5, max_iter=300, snapshot_every=None, verbose=False, print_every=None,
-          logger=None):
+          logger=None, scale=1.0):
     """Minimise ``sum_i f_i(x_i)`` row by row.  ``evaluate(X, rows, row_loss, row_grad)`` writes, for the rows of
     ``rows`` (int32 on the device; ``None``: all), ``row_loss[i] = n_c f_i(X[i])`` (float64) and ``row_grad[i] = grad
     f_i`` (float32), as ``mde_pair_loss_cross_rows`` does.  ``X`` float32 [n, d] on the GPU is the start and is not
@@ -106,7 +112,11 @@ def solve(evaluate, X, n_c, eps=1e-5, max_iter=300, snapshot_every=None, verbose
     Returns a ``RowsResult``.  One entry per sweep in the stats: ``average_distortions`` the mean
     of f over all rows, ``residual_norms`` the Frobenius norm of the joint gradient ``sqrt(sum |g_i|^2) / n``,
     ``step_size_percents`` ``100 |dX|_F / |X|_F``; ``evaluations`` is in units of a full evaluation, the sum of the
-    list lengths over ``n``, the first one included.  A row is still active only when ``max_iter`` ran out."""
+    list lengths over ``n``, the first one included.  A row is still active only when ``max_iter`` ran out.
+
+    ``scale`` multiplies the reported ``value``, ``residual_norm`` and the ``average_distortions`` / ``residual_norms``
+    of the stats, afterwards: a placement that keeps ``p`` of its ``n n_c`` pairs passes ``n n_c / p``, which makes
+    them the joint problem's (mean over the kept pairs).  The solve itself, and ``eps``, do not see it."""
     start_time = time.time()
     n, d, device = int(X.shape[0]), int(X.shape[1]), X.device
     state = RowState(n, d, n_c, eps, device)
@@ -148,6 +158,9 @@ def solve(evaluate, X, n_c, eps=1e-5, max_iter=300, snapshot_every=None, verbose
         values, residuals = table[:, 0].tolist(), table[:, 1].tolist()
         percents = (100.0 * table[:, 2] / table[:, 3]).tolist()
     value, residual = torch.stack([state.f.mean(), state.g.double().square().sum().sqrt() / n]).tolist()
+    if scale != 1.0:
+        values, residuals = [scale * v for v in values], [scale * v for v in residuals]
+        value, residual = scale * value, scale * residual
     stats = optim.SolveStats(values, residuals, percents, time.time() - start_time, times, snapshots, snapshot_every,
                              evaluations=evaluated / float(n))
     return RowsResult(state.x, stats, state.status().to(torch.int32), value, residual)
