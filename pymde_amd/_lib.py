@@ -238,3 +238,11 @@ def ptr(t):
 
 def stream_ptr(device=None):
     return c_vp(torch.cuda.current_stream(device).cuda_stream)
+
+
+def work_buffer(work_bytes, *sizes, device):
+    """The uint8 buffer on ``device`` that one of the library's ``*_work_bytes`` functions asks for at ``sizes``."""
+    nbytes = int(work_bytes(*sizes))
+    if nbytes < 0:
+        check(nbytes)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)

@@ -27,20 +27,21 @@
 //
 // mde_pair_loss_cross is the RECTANGULAR form, what pymde_amd.DensePlacement minimises: the rows
 // are n_q free query rows (Q, XQ), the columns n_c fixed corpus rows (C, XC), D comes from the Gram tile of Q against
-// C or from an [n_q, n_c] matrix, and nothing is "self".  The same kernels: k_pair_loss_walk takes the rows and the
-// columns from two sets of pointers and drops the row != col test at compile time (SELF = false); the fold divides
-// by P = n_q n_c and the total by 1 P instead of 2 P, since every pair is in one row.  No gradient for XC.
+// C or from an [n_q, n_c] matrix, and nothing is "self".  The same kernels: SELF = false drops the row != col test at
+// compile time and makes k_pair_loss_walk take its rows from a LIST; the fold divides by P = n_q n_c and the total by
+// 1 P instead of 2 P, since every pair is in one row.  No gradient for XC.
 //
-// mde_pair_loss_cross_rows is the rectangular walk over a LIST of query rows, what the per-row
-// placement solver (mde_rows.hip) evaluates once its first rows have finished: workgroup x owns the list entries
-// 64 x ..., reads Q, the row norms, XQ and the Dm row through the list (ROWS = true, a compile-time variant of
-// k_pair_loss_walk), and k_pair_loss_fold_rows writes row_loss and row_grad = G / n_c at the rows' own indices.
+// mde_pair_loss_cross_rows is the same walk over a list of query rows that the caller passes, what
+// the per-row placement solver (mde_rows.hip) evaluates once its first rows have finished: workgroup x owns the list
+// entries 64 x ..., reads Q, the row norms, XQ and the Dm row through the list, and the fold writes row_loss and
+// row_grad = G / n_c at the rows' own indices.  mde_pair_loss_cross is this call with no list (every row, in order),
+// the divisor P, and the total.
 //
 // mde_pair_loss_weighted, mde_pair_loss_cross_weighted and mde_pair_loss_cross_rows_weighted are
 // the three calls with a weight per pair -- D^-p formed here, or a matrix W whose zeros are MISSING pairs (WSRC, another
 // compile-time variant of k_pair_loss_walk) -- and with the number of pairs that count passed in.  The unweighted calls
-// launch the WSRC = PAIR_W_NONE instantiations, which are what they were.  mde_pair_weights_check, at the end, is the
-// one pass over W that pymde_amd.dense validates it with.
+// launch the WSRC = PAIR_W_NONE instantiations.  mde_pair_weights_check, at the end, is the one pass over W that
+// pymde_amd.dense validates it with.
 #include <math.h>
 
 #include "mde_pair.h"
@@ -49,7 +50,7 @@
 #define PAIR_LOSS_MAX_D 8
 #define PAIR_LOSS_XS (KNN_BN * PAIR_LOSS_MAX_D)   // floats of the staged column rows of X: 2 KB
 
-// The weight of a pair, a compile-time variant of the walk like ROWS:
+// The weight of a pair, a compile-time variant of the walk:
 //   PAIR_W_NONE    what the walk was: the weighted kinds get a1 = 1 / D^2, nothing else is weighted;
 //   PAIR_W_POWER   w = D^-p from the pair's own D (after d_scale): no per-pair array, either source of D;
 //   PAIR_W_MATRIX  w = W[i][j], a row-major float32 matrix shaped like Dm, whose 64x64 tile is loaded as the Dm
@@ -74,10 +75,10 @@ __device__ __forceinline__ float pair_power_weight(float D, int pclass, float p)
   return powf(D, -p);
 }
 
-// ROWS (mde_pair_loss_cross_rows): the workgroup's 64 rows are the list entries 64 x ... of `rows` (NULL: the rows
-// themselves), n_q is the length of the list, and the partials are indexed by list position.  Without ROWS `rows`
-// is not read and the code is what it was.
-template <int DC, bool MATRIX, bool SELF, bool ROWS = false, int WSRC = PAIR_W_NONE>
+// SELF is the square problem: the workgroup's 64 rows are the rows 64 x ... themselves and `rows` is not read.
+// !SELF is the rectangular one, and its rows come from a LIST: the workgroup's rows are the list entries 64 x ... of
+// `rows` (NULL: the rows themselves), n_q is the length of the list, and the partials are indexed by list position.
+template <int DC, bool MATRIX, bool SELF, int WSRC>
 __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, int nf, int d, int mode,
                                                               int64_t slice_cols, const float* __restrict__ Q,
                                                               const float* __restrict__ qn,
@@ -89,8 +90,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
                                                               MdeScalars S, float d_scale,
                                                               double* __restrict__ part,
                                                               const int32_t* __restrict__ rows, PairWeights wt) {
-  static_assert(!(SELF && ROWS), "the row list belongs to the rectangular walk");
-  constexpr bool WMAT = WSRC == PAIR_W_MATRIX;
+  constexpr bool WMAT = WSRC == PAIR_W_MATRIX, ROWS = !SELF;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const knn_tile_lds s = knn_tile_carve(lds, 0, PAIR_TILE + PAIR_LOSS_XS + (ROWS ? KNN_BM : 0));
   float* sW = s.extra;                                          // [KNN_BM][KNN_BN + 1] the weights of the tile (WMAT)
@@ -263,32 +263,15 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_walk(int n_q, int n_c, 
 static_assert(4 * KNN_BM * (1 + PAIR_LOSS_MAX_D) * sizeof(double) <= 2 * PAIR_TILE * sizeof(float),
               "the row partials must fit in the parked tile and the tile after it");
 
-// row_loss[i] and grad[i, :] = G[i, :] / pairs from the per-slice partials [slices, n, 1 + d], added in slice order
-// (n rows: the rows of the square problem, the query rows of the rectangular one).
-__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold(int64_t n, int d, int slices, double pairs,
+// row_loss[row] and grad[row, :] = G / divisor from the per-slice partials [slices, n_rows, 1 + d], added in slice
+// order.  The partials are indexed by list position, the outputs by the row itself (`rows`; NULL: the position is the
+// row, as in the square problem).  The divisor is P for the joint calls and n_c for the list calls, so that there a
+// row's result does not depend on the list it came in.
+__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold(int64_t n_rows, int d, int slices, double divisor,
                                                               const double* __restrict__ part,
+                                                              const int32_t* __restrict__ rows,
                                                               double* __restrict__ row_loss,
                                                               float* __restrict__ grad) {
-  const int64_t total = n * (1 + d);
-  for (int64_t i = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * MDE_BLOCK) {
-    double t = 0.0;
-    for (int y = 0; y < slices; ++y) t += part[(int64_t)y * total + i];
-    const int64_t row = i / (1 + d);
-    const int v = (int)(i - row * (1 + d));
-    if (v == 0)
-      row_loss[row] = t;
-    else
-      grad[row * d + v - 1] = (float)(t / pairs);
-  }
-}
-
-// The fold of mde_pair_loss_cross_rows: the partials [slices, n_rows, 1 + d] are indexed by list position, the
-// outputs by the row itself; row_grad = G / n_c, so a row's result does not depend on the list it came in.
-__global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold_rows(int64_t n_rows, int d, int slices, double n_c,
-                                                                   const double* __restrict__ part,
-                                                                   const int32_t* __restrict__ rows,
-                                                                   double* __restrict__ row_loss,
-                                                                   float* __restrict__ row_grad) {
   const int64_t total = n_rows * (1 + d);
   for (int64_t i = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * MDE_BLOCK) {
     double t = 0.0;
@@ -299,7 +282,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_pair_loss_fold_rows(int64_t n_row
     if (v == 0)
       row_loss[row] = t;
     else
-      row_grad[row * d + v - 1] = (float)(t / n_c);
+      grad[row * d + v - 1] = (float)(t / divisor);
   }
 }
 
@@ -354,66 +337,69 @@ extern "C" int64_t mde_pair_loss_cross_work_bytes(int64_t n_q, int64_t n_c, int3
   return s * n_q * (1 + d) * 8 + 4 * (n_q + n_c);
 }
 
-template <int DC, bool SELF, bool ROWS, int WSRC>
-static void pair_loss_launch_dc(bool matrix, dim3 grid, hipStream_t st, int n_q, int n_c, int nf, int d, int mode,
-                                int64_t slice_cols, const float* Q, const float* qn, const float* C, const float* cn,
-                                const float* Dm, const float* XQ, const float* XC, int kind, MdeScalars S,
-                                float d_scale, double* part, const int32_t* rows, PairWeights wt) {
-  const size_t lds = knn_tile_lds_bytes(0, PAIR_TILE + PAIR_LOSS_XS + (ROWS ? KNN_BM : 0));
-  const int weighted = kind == MDE_F_L_WEIGHTED_QUADRATIC || kind == MDE_F_L_WEIGHTED_POWER;
-  if (matrix)
-    hipLaunchKernelGGL((k_pair_loss_walk<DC, true, SELF, ROWS, WSRC>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf, d,
-                       mode, slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part, rows, wt);
-  else
-    hipLaunchKernelGGL((k_pair_loss_walk<DC, false, SELF, ROWS, WSRC>), grid, dim3(MDE_BLOCK), lds, st, n_q, n_c, nf,
-                       d, mode, slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, weighted, S, d_scale, part, rows, wt);
-}
+// The arguments of one walk, filled once per entry point: n_q rows (the rectangular problem: list entries, the rows of
+// `rows`) against the n_c columns in s slices; part [s, n_q, 1 + d]; qn / cn are read by the Gram source only, and a
+// non-null Dm is the matrix source.
+struct PairWalk {
+  int64_t n_q, n_c;
+  int32_t nf, mode;
+  const float *Q, *qn, *C, *cn, *Dm;
+  float d_scale;
+  int32_t d;
+  const float *XQ, *XC;
+  int32_t kind;
+  MdeScalars S;
+  int64_t s;
+  double* part;
+  const int32_t* rows;
+  int32_t wsrc;
+  PairWeights wt;
+  hipStream_t st;
+};
 
-template <int DC, bool SELF, bool ROWS>
-static void pair_loss_launch_w(int wsrc, bool matrix, dim3 grid, hipStream_t st, int n_q, int n_c, int nf, int d,
-                               int mode, int64_t slice_cols, const float* Q, const float* qn, const float* C,
-                               const float* cn, const float* Dm, const float* XQ, const float* XC, int kind,
-                               MdeScalars S, float d_scale, double* part, const int32_t* rows, PairWeights wt) {
-  if (wsrc == PAIR_W_MATRIX)
-    pair_loss_launch_dc<DC, SELF, ROWS, PAIR_W_MATRIX>(matrix, grid, st, n_q, n_c, nf, d, mode, slice_cols, Q, qn, C,
-                                                       cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
-  else if (wsrc == PAIR_W_POWER)
-    pair_loss_launch_dc<DC, SELF, ROWS, PAIR_W_POWER>(matrix, grid, st, n_q, n_c, nf, d, mode, slice_cols, Q, qn, C,
-                                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
-  else
-    pair_loss_launch_dc<DC, SELF, ROWS, PAIR_W_NONE>(matrix, grid, st, n_q, n_c, nf, d, mode, slice_cols, Q, qn, C, cn,
-                                                     Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
-}
-
-// The walk of either problem on checked arguments: n_q rows (ROWS: list entries, the rows of `rows`) against the n_c
-// columns in s slices; part [s, n_q, 1 + d]; qn / cn are read by the Gram source only.
-template <bool SELF, bool ROWS>
-static int pair_loss_walk(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* qn, const float* C,
-                          const float* cn, int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
-                          const float* XC, int32_t kind, MdeScalars S, int64_t s, double* part, const int32_t* rows,
-                          int wsrc, PairWeights wt, hipStream_t st) {
-  const int64_t tiles = (n_c + KNN_BN - 1) / KNN_BN;
-  const int64_t slice_cols = ((tiles + s - 1) / s) * KNN_BN;     // whole tiles; the last slices may be short or empty
-  const dim3 grid((unsigned)((n_q + KNN_BM - 1) / KNN_BM), (unsigned)s);
-  const bool matrix = Dm != nullptr;
-  if (d == 1)
-    pair_loss_launch_w<1, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
-                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
-  else if (d == 2)
-    pair_loss_launch_w<2, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
-                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
-  else if (d == 3)
-    pair_loss_launch_w<3, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode, slice_cols, Q, qn, C,
-                                      cn, Dm, XQ, XC, kind, S, d_scale, part, rows, wt);
-  else
-    pair_loss_launch_w<PAIR_LOSS_MAX_D, SELF, ROWS>(wsrc, matrix, grid, st, (int)n_q, (int)n_c, nf, d, mode,
-                                                    slice_cols, Q, qn, C, cn, Dm, XQ, XC, kind, S, d_scale, part,
-                                                    rows, wt);
+// The one launch of the walk: the instantiation <DC, MATRIX, SELF, WSRC> is looked up, not branched to.
+// (PAIR_WALK_WIDTHS takes SELF from the template it is used in.)
+using PairWalkKernel = decltype(&k_pair_loss_walk<1, false, true, PAIR_W_NONE>);
+static_assert(PAIR_W_NONE == 0 && PAIR_W_POWER == 1 && PAIR_W_MATRIX == 2, "the weight source indexes the kernels");
+#define PAIR_WALK_WIDTHS(MATRIX, WSRC)                                                   \
+  {k_pair_loss_walk<1, MATRIX, SELF, WSRC>, k_pair_loss_walk<2, MATRIX, SELF, WSRC>,     \
+   k_pair_loss_walk<3, MATRIX, SELF, WSRC>, k_pair_loss_walk<PAIR_LOSS_MAX_D, MATRIX, SELF, WSRC>}
+template <bool SELF>
+static int pair_loss_walk(const PairWalk& a) {
+  static const PairWalkKernel kernels[2][3][4] = {
+      {PAIR_WALK_WIDTHS(false, PAIR_W_NONE), PAIR_WALK_WIDTHS(false, PAIR_W_POWER),
+       PAIR_WALK_WIDTHS(false, PAIR_W_MATRIX)},
+      {PAIR_WALK_WIDTHS(true, PAIR_W_NONE), PAIR_WALK_WIDTHS(true, PAIR_W_POWER),
+       PAIR_WALK_WIDTHS(true, PAIR_W_MATRIX)}};
+  const int64_t tiles = (a.n_c + KNN_BN - 1) / KNN_BN;
+  const int64_t slice_cols = ((tiles + a.s - 1) / a.s) * KNN_BN;   // whole tiles; the last slices may be short or empty
+  const dim3 grid((unsigned)((a.n_q + KNN_BM - 1) / KNN_BM), (unsigned)a.s);
+  const size_t lds = knn_tile_lds_bytes(0, PAIR_TILE + PAIR_LOSS_XS + (SELF ? 0 : KNN_BM));
+  const int weighted = a.kind == MDE_F_L_WEIGHTED_QUADRATIC || a.kind == MDE_F_L_WEIGHTED_POWER;
+  const int width = a.d <= 3 ? a.d - 1 : 3;                         // DC = d padded to 1, 2, 3 or 8
+  hipLaunchKernelGGL(kernels[a.Dm != nullptr][a.wsrc][width], grid, dim3(MDE_BLOCK), lds, a.st, (int)a.n_q,
+                     (int)a.n_c, a.nf, a.d, a.mode, slice_cols, a.Q, a.qn, a.C, a.cn, a.Dm, a.XQ, a.XC, a.kind, weighted,
+                     a.S, a.d_scale, a.part, a.rows, a.wt);
   MDE_LAUNCH_CHECK();
   return MDE_OK;
 }
+#undef PAIR_WALK_WIDTHS
 
-// The weight arguments of the *_weighted entry points; `pairs` < 0 where the entry point has none.
+// The fold of a walk and, where `loss` is asked for, the total over its n_q rows: loss = sum row_loss / (factor *
+// divisor), factor 2 for the square problem, where every pair is in two rows, 1 for the rectangular one.
+static int pair_loss_fold(const PairWalk& a, double divisor, double factor, double* loss, double* row_loss,
+                          float* grad) {
+  hipLaunchKernelGGL(k_pair_loss_fold, dim3(mde_grid(a.n_q * (1 + a.d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, a.st,
+                     a.n_q, (int)a.d, (int)a.s, divisor, a.part, a.rows, row_loss, grad);
+  MDE_LAUNCH_CHECK();
+  if (loss) {
+    hipLaunchKernelGGL(k_pair_loss_total, dim3(1), dim3(MDE_BLOCK), 0, a.st, a.n_q, divisor, factor, row_loss, loss);
+    MDE_LAUNCH_CHECK();
+  }
+  return MDE_OK;
+}
+
+// The weight arguments of the *_weighted entry points; `pairs` is looked at where the entry point has one.
 static bool pair_weights_ok(const char* fn, int32_t wsrc, float p, const float* W, bool has_pairs, double pairs) {
   const bool source_ok = wsrc == PAIR_W_NONE || wsrc == PAIR_W_POWER || wsrc == PAIR_W_MATRIX;
   const bool w_ok = wsrc == PAIR_W_MATRIX ? W != nullptr : W == nullptr;
@@ -431,25 +417,8 @@ static PairWeights pair_weights(int32_t wsrc, float p, const float* W) {
   return wt;
 }
 
-// The walk, the fold and the total of either problem on checked arguments: SELF is the square problem (rows and
-// columns are the same items, the diagonal is left out, every pair is in two rows), !SELF the rectangular one.
-template <bool SELF>
-static int pair_loss_run(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* qn, const float* C,
-                         const float* cn, int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
-                         const float* XC, int32_t kind, MdeScalars S, int64_t s, int wsrc, PairWeights wt,
-                         double pairs, double* loss, float* grad, double* row_loss, double* part, hipStream_t st) {
-  const int rc = pair_loss_walk<SELF, false>(n_q, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s,
-                                             part, nullptr, wsrc, wt, st);
-  if (rc != MDE_OK) return rc;
-  hipLaunchKernelGGL(k_pair_loss_fold, dim3(mde_grid(n_q * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n_q,
-                     (int)d, (int)s, pairs, part, row_loss, grad);
-  MDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_pair_loss_total, dim3(1), dim3(MDE_BLOCK), 0, st, n_q, pairs, SELF ? 2.0 : 1.0, row_loss, loss);
-  MDE_LAUNCH_CHECK();
-  return MDE_OK;
-}
-
-// The square problem behind mde_pair_loss (no weights, pairs = n (n - 1) / 2) and mde_pair_loss_weighted.
+// The square problem behind mde_pair_loss (no weights, pairs = n (n - 1) / 2) and mde_pair_loss_weighted: rows and
+// columns are the same items, the diagonal is left out.
 static int pair_loss_square(const char* fn, int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm,
                             float d_scale, int32_t d, const float* X, int32_t kind, float s0, float s1, float s2,
                             int32_t slices, int32_t wsrc, float p, const float* W, double pairs, double* loss,
@@ -471,9 +440,14 @@ static int pair_loss_square(const char* fn, int64_t n, int32_t nf, const float* 
     const int rc = mde_row_sqnorm(n, nf, A, an, stream);
     if (rc != MDE_OK) return rc;
   }
-  const MdeScalars S = {s0, s1, s2};
-  return pair_loss_run<true>(n, n, nf, A, an, A, an, mode, Dm, d_scale, d, X, X, kind, S, s, wsrc,
-                             pair_weights(wsrc, p, W), pairs, loss, grad, row_loss, part, mde_stream(stream));
+  PairWalk a;
+  a.n_q = n, a.n_c = n, a.nf = nf, a.mode = mode;
+  a.Q = A, a.qn = an, a.C = A, a.cn = an, a.Dm = Dm;
+  a.d_scale = d_scale, a.d = d, a.XQ = X, a.XC = X, a.kind = kind, a.S = MdeScalars{s0, s1, s2};
+  a.s = s, a.part = part, a.rows = nullptr;
+  a.wsrc = wsrc, a.wt = pair_weights(wsrc, p, W), a.st = mde_stream(stream);
+  const int rc = pair_loss_walk<true>(a);
+  return rc != MDE_OK ? rc : pair_loss_fold(a, pairs, 2.0, loss, row_loss, grad);
 }
 
 extern "C" int mde_pair_loss(int64_t n, int32_t nf, const float* A, int32_t mode, const float* Dm, float d_scale,
@@ -490,57 +464,6 @@ extern "C" int mde_pair_loss_weighted(int64_t n, int32_t nf, const float* A, int
                                       double* loss, float* grad, double* row_loss, void* work, void* stream) {
   return pair_loss_square("mde_pair_loss_weighted", n, nf, A, mode, Dm, d_scale, d, X, kind, s0, s1, s2, slices,
                           wsource, p, W, pairs, loss, grad, row_loss, work, stream);
-}
-
-// The rectangular problem: every (query row, corpus row) pair, a gradient for the query rows only.
-static int pair_loss_rect(const char* fn, int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
-                          int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
-                          int32_t kind, float s0, float s1, float s2, int32_t slices, int32_t wsrc, float p,
-                          const float* W, double pairs, double* loss, float* grad, double* row_loss, void* work,
-                          void* stream) {
-  const bool gram = Q != nullptr && C != nullptr && Dm == nullptr;
-  const bool matrix = Q == nullptr && C == nullptr && Dm != nullptr;
-  const bool source_ok = matrix || (gram && nf >= 1 && (mode == 0 || mode == 1));
-  if (!pair_loss_cross_args_ok(n_q, n_c, d, slices) || !source_ok || !pair_loss_kind_ok(kind) || !(d_scale > 0.0f) ||
-      !isfinite(d_scale) || !XQ || !XC || !loss || !grad || !row_loss || !work) {
-    mde_set_error("%s: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and C (nf "
-                  ">= 1, mode 0 / 1) or Dm alone, kind one of the MDE_F_L_* losses, d_scale positive and finite, 0 <= "
-                  "slices <= %d, non-null XQ / XC / outputs / work)", fn, PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
-    return MDE_E_INVALID;
-  }
-  if (!pair_weights_ok(fn, wsrc, p, W, true, pairs)) return MDE_E_INVALID;
-  const int64_t s = cross_resolve_slices(n_q, n_c, slices);
-  if (s < 0) return (int)s;
-  double* part = static_cast<double*>(work);
-  float* qn = reinterpret_cast<float*>(part + s * n_q * (1 + d));
-  float* cn = qn + n_q;
-  if (gram) {
-    int rc = mde_row_sqnorm(n_q, nf, Q, qn, stream);
-    if (rc == MDE_OK) rc = mde_row_sqnorm(n_c, nf, C, cn, stream);
-    if (rc != MDE_OK) return rc;
-  }
-  const MdeScalars S = {s0, s1, s2};
-  return pair_loss_run<false>(n_q, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s, wsrc,
-                              pair_weights(wsrc, p, W), pairs, loss, grad, row_loss, part, mde_stream(stream));
-}
-
-extern "C" int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
-                                   const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
-                                   int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
-                                   float* grad, double* row_loss, void* work, void* stream) {
-  return pair_loss_rect("mde_pair_loss_cross", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0, s1, s2,
-                        slices, PAIR_W_NONE, 0.0f, nullptr, (double)n_q * (double)n_c, loss, grad, row_loss, work,
-                        stream);
-}
-
-// mde_pair_loss_cross with a weight per pair, W [n_q, n_c], and the count of the pairs that count passed in.
-extern "C" int mde_pair_loss_cross_weighted(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
-                                            int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
-                                            const float* XC, int32_t kind, float s0, float s1, float s2,
-                                            int32_t slices, int32_t wsource, float p, const float* W, double pairs,
-                                            double* loss, float* grad, double* row_loss, void* work, void* stream) {
-  return pair_loss_rect("mde_pair_loss_cross_weighted", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0,
-                        s1, s2, slices, wsource, p, W, pairs, loss, grad, row_loss, work, stream);
 }
 
 // The most list entries times slices the walk of mde_pair_loss_cross_rows can hold partials for, over every list
@@ -571,28 +494,32 @@ extern "C" int64_t mde_pair_loss_cross_rows_work_bytes(int64_t n_q, int64_t n_c,
   return part_rows * (1 + d) * 8 + 4 * (n_q + n_c);
 }
 
-// The rectangular problem over a list of query rows: per-row sums only, written at the rows' own indices.
-static int pair_loss_rect_rows(const char* fn, int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
-                               int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
-                               const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
-                               int64_t n_rows, const int32_t* rows, int32_t wsrc, float p, const float* W,
-                               double* row_loss, float* row_grad, void* work, void* stream) {
+// The rectangular problem: the (query row, corpus row) pairs of the n_rows query rows of `rows` (NULL: all n_q), a
+// gradient for the query rows only, the per-row sums written at the rows' own indices.  The JOINT calls
+// (mde_pair_loss_cross and its weighted form) have no list: all rows, partials as mde_pair_loss_cross_work_bytes lays
+// them out, the gradient divided by `pairs`, and the total.  The list calls divide by n_c and have neither `pairs`
+// nor `loss`.
+static int pair_loss_rect(const char* fn, bool joint, int64_t n_q, int64_t n_c, int32_t nf, const float* Q,
+                          const float* C, int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                          const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices, int64_t n_rows,
+                          const int32_t* rows, int32_t wsrc, float p, const float* W, double pairs, double* loss,
+                          double* row_loss, float* row_grad, void* work, void* stream) {
   const bool gram = Q != nullptr && C != nullptr && Dm == nullptr;
   const bool matrix = Q == nullptr && C == nullptr && Dm != nullptr;
   const bool source_ok = matrix || (gram && nf >= 1 && (mode == 0 || mode == 1));
-  const bool rows_ok = n_rows >= 1 && n_rows <= n_q && (rows != nullptr || n_rows == n_q);
+  const bool rows_ok = joint || (n_rows >= 1 && n_rows <= n_q && (rows != nullptr || n_rows == n_q));
   if (!pair_loss_cross_args_ok(n_q, n_c, d, slices) || !source_ok || !rows_ok || !pair_loss_kind_ok(kind) ||
-      !(d_scale > 0.0f) || !isfinite(d_scale) || !XQ || !XC || !row_loss || !row_grad || !work) {
-    mde_set_error("%s: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and "
-                  "C (nf >= 1, mode 0 / 1) or Dm alone, kind one of the MDE_F_L_* losses, d_scale positive and finite, "
-                  "0 <= slices <= %d, 1 <= n_rows <= n_q and n_rows == n_q without rows, non-null XQ / XC / outputs / "
-                  "work)", fn, PAIR_LOSS_MAX_D, CROSS_MAX_SLICES);
+      !(d_scale > 0.0f) || !isfinite(d_scale) || !XQ || !XC || (joint && !loss) || !row_loss || !row_grad || !work) {
+    mde_set_error("%s: invalid arguments (1 <= n_q, n_c < 2^31, 1 <= d <= %d, either both Q and C (nf >= 1, mode 0 / "
+                  "1) or Dm alone, kind one of the MDE_F_L_* losses, d_scale positive and finite, 0 <= slices <= %d, "
+                  "%snon-null XQ / XC / outputs / work)", fn, PAIR_LOSS_MAX_D, CROSS_MAX_SLICES,
+                  joint ? "" : "1 <= n_rows <= n_q and n_rows == n_q without rows, ");
     return MDE_E_INVALID;
   }
-  if (!pair_weights_ok(fn, wsrc, p, W, false, 0.0)) return MDE_E_INVALID;
+  if (!pair_weights_ok(fn, wsrc, p, W, joint, pairs)) return MDE_E_INVALID;
   const int64_t s = cross_resolve_slices(n_rows, n_c, slices);
   if (s < 0) return (int)s;
-  const int64_t part_rows = pair_loss_rows_part_rows(n_q, n_c, slices);
+  const int64_t part_rows = joint ? s * n_q : pair_loss_rows_part_rows(n_q, n_c, slices);
   if (part_rows < 0) return (int)part_rows;
   double* part = static_cast<double*>(work);
   float* qn = reinterpret_cast<float*>(part + part_rows * (1 + d));
@@ -602,15 +529,33 @@ static int pair_loss_rect_rows(const char* fn, int64_t n_q, int64_t n_c, int32_t
     if (rc == MDE_OK) rc = mde_row_sqnorm(n_c, nf, C, cn, stream);
     if (rc != MDE_OK) return rc;
   }
-  const MdeScalars S = {s0, s1, s2};
-  hipStream_t st = mde_stream(stream);
-  const int rc = pair_loss_walk<false, true>(n_rows, n_c, nf, Q, qn, C, cn, mode, Dm, d_scale, d, XQ, XC, kind, S, s,
-                                             part, rows, wsrc, pair_weights(wsrc, p, W), st);
-  if (rc != MDE_OK) return rc;
-  hipLaunchKernelGGL(k_pair_loss_fold_rows, dim3(mde_grid(n_rows * (1 + d), MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st,
-                     n_rows, (int)d, (int)s, (double)n_c, part, rows, row_loss, row_grad);
-  MDE_LAUNCH_CHECK();
-  return MDE_OK;
+  PairWalk a;
+  a.n_q = n_rows, a.n_c = n_c, a.nf = nf, a.mode = mode;
+  a.Q = Q, a.qn = qn, a.C = C, a.cn = cn, a.Dm = Dm;
+  a.d_scale = d_scale, a.d = d, a.XQ = XQ, a.XC = XC, a.kind = kind, a.S = MdeScalars{s0, s1, s2};
+  a.s = s, a.part = part, a.rows = rows;
+  a.wsrc = wsrc, a.wt = pair_weights(wsrc, p, W), a.st = mde_stream(stream);
+  const int rc = pair_loss_walk<false>(a);
+  return rc != MDE_OK ? rc : pair_loss_fold(a, joint ? pairs : (double)n_c, 1.0, loss, row_loss, row_grad);
+}
+
+extern "C" int mde_pair_loss_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                                   const float* Dm, float d_scale, int32_t d, const float* XQ, const float* XC,
+                                   int32_t kind, float s0, float s1, float s2, int32_t slices, double* loss,
+                                   float* grad, double* row_loss, void* work, void* stream) {
+  return pair_loss_rect("mde_pair_loss_cross", true, n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0, s1,
+                        s2, slices, n_q, nullptr, PAIR_W_NONE, 0.0f, nullptr, (double)n_q * (double)n_c, loss,
+                        row_loss, grad, work, stream);
+}
+
+// mde_pair_loss_cross with a weight per pair, W [n_q, n_c], and the count of the pairs that count passed in.
+extern "C" int mde_pair_loss_cross_weighted(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
+                                            int32_t mode, const float* Dm, float d_scale, int32_t d, const float* XQ,
+                                            const float* XC, int32_t kind, float s0, float s1, float s2,
+                                            int32_t slices, int32_t wsource, float p, const float* W, double pairs,
+                                            double* loss, float* grad, double* row_loss, void* work, void* stream) {
+  return pair_loss_rect("mde_pair_loss_cross_weighted", true, n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind,
+                        s0, s1, s2, slices, n_q, nullptr, wsource, p, W, pairs, loss, row_loss, grad, work, stream);
 }
 
 extern "C" int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C,
@@ -618,9 +563,9 @@ extern "C" int mde_pair_loss_cross_rows(int64_t n_q, int64_t n_c, int32_t nf, co
                                         const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
                                         int64_t n_rows, const int32_t* rows, double* row_loss, float* row_grad,
                                         void* work, void* stream) {
-  return pair_loss_rect_rows("mde_pair_loss_cross_rows", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0,
-                             s1, s2, slices, n_rows, rows, PAIR_W_NONE, 0.0f, nullptr, row_loss, row_grad, work,
-                             stream);
+  return pair_loss_rect("mde_pair_loss_cross_rows", false, n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC, kind, s0,
+                        s1, s2, slices, n_rows, rows, PAIR_W_NONE, 0.0f, nullptr, 0.0, nullptr, row_loss, row_grad,
+                        work, stream);
 }
 
 // mde_pair_loss_cross_rows with a weight per pair; W [n_q, n_c] is read through the list as Dm is.  The divisor
@@ -631,8 +576,9 @@ extern "C" int mde_pair_loss_cross_rows_weighted(int64_t n_q, int64_t n_c, int32
                                                  float s2, int32_t slices, int64_t n_rows, const int32_t* rows,
                                                  int32_t wsource, float p, const float* W, double* row_loss,
                                                  float* row_grad, void* work, void* stream) {
-  return pair_loss_rect_rows("mde_pair_loss_cross_rows_weighted", n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC,
-                             kind, s0, s1, s2, slices, n_rows, rows, wsource, p, W, row_loss, row_grad, work, stream);
+  return pair_loss_rect("mde_pair_loss_cross_rows_weighted", false, n_q, n_c, nf, Q, C, mode, Dm, d_scale, d, XQ, XC,
+                        kind, s0, s1, s2, slices, n_rows, rows, wsource, p, W, 0.0, nullptr, row_loss, row_grad, work,
+                        stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

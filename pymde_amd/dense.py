@@ -209,10 +209,7 @@ def _pair_loss(X, spec, A=None, mode=0, Dm=None, d_scale=1.0, slices=0, work=Non
 
 
 def _work(lib, n, d, slices, device):
-    nbytes = int(lib.mde_pair_loss_work_bytes(n, d, slices))
-    if nbytes < 0:
-        _lib.check(nbytes)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _lib.work_buffer(lib.mde_pair_loss_work_bytes, n, d, slices, device=device)
 
 
 class _DenseDistortion(torch.autograd.Function):
@@ -230,23 +227,26 @@ class _DenseDistortion(torch.autograd.Function):
         return grad_output * grad, None
 
 
-def _check_distance_matrix(D):
-    """Finite, non-negative, symmetric: one pass on the GPU in row blocks, one read-back; ``ValueError`` saying which."""
-    n = int(D.shape[0])
+def _check_distance_matrix(D, square=True):
+    """Finite and non-negative and, for a ``square`` matrix, symmetric (a rectangular one has no symmetry to check): one
+    pass on the GPU in row blocks, one read-back; ``ValueError`` saying which."""
+    rows, cols = int(D.shape[0]), int(D.shape[1])
     flags = torch.zeros(2, dtype=torch.int64, device=D.device)
     worst = torch.zeros(2, dtype=torch.float32, device=D.device)          # the largest entry, the largest |D - D^T|
-    step = max(1, min(n, (1 << 24) // n))
-    for lo in range(0, n, step):
+    step = max(1, min(rows, (1 << 24) // cols))
+    for lo in range(0, rows, step):
         block = D[lo:lo + step]
         flags[0] += (~torch.isfinite(block)).sum()
         flags[1] += (block < 0).sum()
-        worst[0] = torch.maximum(worst[0], block.abs().max())
-        worst[1] = torch.maximum(worst[1], (block - D[:, lo:lo + step].T).abs().max())
-    (bad, negative), (top, asym) = flags.tolist(), worst.tolist()
+        if square:
+            worst[0] = torch.maximum(worst[0], block.abs().max())
+            worst[1] = torch.maximum(worst[1], (block - D[:, lo:lo + step].T).abs().max())
+    bad, negative = flags.tolist()
     if bad:
         raise ValueError(f"`distance_matrix` is not finite: {bad} of its entries are NaN or infinite")
     if negative:
         raise ValueError(f"`distance_matrix` is not non-negative: {negative} of its entries are below zero")
+    top, asym = worst.tolist() if square else (0.0, 0.0)
     if asym > SYMMETRY_RTOL * top:
         raise ValueError(f"`distance_matrix` is not symmetric: an entry differs from its mirror image by {asym:.3g} "
                          f"(the largest entry is {top:.3g})")
@@ -289,14 +289,8 @@ class DenseMDE(object):
                  metric="euclidean", deviation_scale=1.0, device=None, weights=None):
         if (data is None) == (distance_matrix is None):
             raise ValueError("exactly one of `data` and `distance_matrix` must be given")
-        embedding_dim = int(embedding_dim)
-        if not 1 <= embedding_dim <= MAX_DIM:
-            raise ValueError(f"embedding_dim must lie in [1, {MAX_DIM}] for a dense problem (the kernel keeps a "
-                             f"row of the embedding in registers), got {embedding_dim}")
-        self._spec = loss_spec(loss)
-        deviation_scale = float(deviation_scale)
-        if not (deviation_scale > 0.0 and math.isfinite(deviation_scale)):
-            raise ValueError(f"deviation_scale must be a positive finite number, got {deviation_scale!r}")
+        self._set_loss(int(embedding_dim), loss, deviation_scale, "embedding_dim",
+                       " (the kernel keeps a row of the embedding in registers)")
         source = data if data is not None else distance_matrix
         if data is not None:
             metric = check_source(data, metric)
@@ -320,22 +314,42 @@ class DenseMDE(object):
             if weights.source != W_MATRIX:
                 _check_distance_matrix(self._Dm)
         self.n_items = n
-        self.embedding_dim = embedding_dim
+        self._item_pairs = n - 1
         self.n_all_pairs = n * (n - 1) // 2
+        self._set_weights(weights, True)
+        self.metric = metric if data is not None else None
+        self.constraint = constraints.Centered() if constraint is None else constraint
+        self._reset()
+
+    # ------------------------------------------------------------------ what the constructors of both problems share
+    def _set_loss(self, embedding_dim, loss, deviation_scale, dimension, reason):
+        """Checks and installs ``embedding_dim``, ``loss`` (and its ``_spec``) and ``deviation_scale``; the message
+        names the dimension as ``dimension`` and adds ``reason``."""
+        if not 1 <= embedding_dim <= MAX_DIM:
+            raise ValueError(f"{dimension} must lie in [1, {MAX_DIM}] for a dense problem{reason}, got "
+                             f"{embedding_dim}")
+        self._spec = loss_spec(loss)
+        deviation_scale = float(deviation_scale)
+        if not (deviation_scale > 0.0 and math.isfinite(deviation_scale)):
+            raise ValueError(f"deviation_scale must be a positive finite number, got {deviation_scale!r}")
+        self.embedding_dim, self.loss, self.deviation_scale = embedding_dim, loss, deviation_scale
+
+    def _set_weights(self, weights, square):
+        """Installs a ``parse_weights`` result (a matrix goes to the device and is checked, with ``_Dm``): ``_weights``,
+        ``_row_kept`` and ``p``, the number of pairs that count."""
         self.p = self.n_all_pairs
         self._weights, self._row_kept = (None if weights.source == W_NONE else weights), None
         if weights.source == W_MATRIX:
-            self._weights, stats = _device_weights(weights, self._Dm, True, self.device)
+            self._weights, stats = _device_weights(weights, self._Dm, square, self.device)
             self.p, self._row_kept = int(stats.kept), stats.row_kept
-        self.metric = metric if data is not None else None
-        self.deviation_scale = deviation_scale
-        self.loss = loss
-        self.constraint = constraints.Centered() if constraint is None else constraint
+
+    def _reset(self):
         self.X = None
         self.solve_stats = None
         self.value = None
         self.residual_norm = None
         self._work_buffer = None
+        self._rows_work_buffer = None
 
     def __str__(self):
         source = "data matrix, metric %s" % self.metric if self._A is not None else "distance matrix"
@@ -390,13 +404,13 @@ class DenseMDE(object):
         return _DenseDistortion.apply(self._embedding_arg(X), self)
 
     def item_distortions(self, X=None):
-        """float32 [n]: for every item the mean of the loss over its ``n - 1`` pairs (colour a plot by it).  Their
-        mean is the average distortion.  With a weight matrix: over the pairs the item keeps (their mean, weighted
-        by those counts, is then the average distortion)."""
+        """float32 [n]: for every item the mean of the loss over its pairs (colour a plot by it) -- ``n - 1`` of them,
+        ``n_old`` for a new row of a placement.  Their mean is the average distortion.  With a weight matrix: over the
+        pairs the item keeps (their mean, weighted by those counts, is then the average distortion)."""
         row_loss = self._evaluate(self._embedding_arg(X).detach())[2]
         if self._row_kept is not None:
             return (row_loss / self._row_kept.to(torch.float64)).to(torch.float32)
-        return (row_loss / float(self.n_items - 1)).to(torch.float32)
+        return (row_loss / float(self._item_pairs)).to(torch.float32)
 
     @classmethod
     def from_graph(cls, graph, embedding_dim=2, loss=losses.Absolute, constraint=None, max_length=None):
@@ -494,27 +508,7 @@ def _pair_loss_cross(XQ, XC, spec, Q=None, C=None, mode=0, Dm=None, d_scale=1.0,
 
 
 def _work_cross(lib, n_q, n_c, d, slices, device):
-    nbytes = int(lib.mde_pair_loss_cross_work_bytes(n_q, n_c, d, slices))
-    if nbytes < 0:
-        _lib.check(nbytes)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
-def _check_rectangular_matrix(D):
-    """Finite and non-negative (a rectangular matrix has no symmetry to check): one pass on the GPU in row blocks,
-    one read-back; ``ValueError`` saying which."""
-    rows, cols = int(D.shape[0]), int(D.shape[1])
-    flags = torch.zeros(2, dtype=torch.int64, device=D.device)
-    step = max(1, min(rows, (1 << 24) // cols))
-    for lo in range(0, rows, step):
-        block = D[lo:lo + step]
-        flags[0] += (~torch.isfinite(block)).sum()
-        flags[1] += (block < 0).sum()
-    bad, negative = flags.tolist()
-    if bad:
-        raise ValueError(f"`distance_matrix` is not finite: {bad} of its entries are NaN or infinite")
-    if negative:
-        raise ValueError(f"`distance_matrix` is not non-negative: {negative} of its entries are below zero")
+    return _lib.work_buffer(lib.mde_pair_loss_cross_work_bytes, n_q, n_c, d, slices, device=device)
 
 
 class _Free(constraints.Constraint):
@@ -594,13 +588,7 @@ class DensePlacement(DenseMDE):
             raise ValueError("`X` must be the embedding [n_old, d] of the embedded rows, got shape "
                              f"{tuple(getattr(X, 'shape', ()))}")
         n_old, embedding_dim = int(X.shape[0]), int(X.shape[1])
-        if not 1 <= embedding_dim <= MAX_DIM:
-            raise ValueError(f"the embedding dimension (the columns of `X`) must lie in [1, {MAX_DIM}] for a dense "
-                             f"problem, got {embedding_dim}")
-        self._spec = loss_spec(loss)
-        deviation_scale = float(deviation_scale)
-        if not (deviation_scale > 0.0 and math.isfinite(deviation_scale)):
-            raise ValueError(f"deviation_scale must be a positive finite number, got {deviation_scale!r}")
+        self._set_loss(embedding_dim, loss, deviation_scale, "the embedding dimension (the columns of `X`)", "")
         if from_data:
             for m in (data, new_data):
                 metric = check_source(m, metric)
@@ -648,27 +636,15 @@ class DensePlacement(DenseMDE):
         else:
             self._Dm = torch.as_tensor(distance_matrix).to(device=self.device, dtype=torch.float32).contiguous()
             if weights.source != W_MATRIX:
-                _check_rectangular_matrix(self._Dm)
+                _check_distance_matrix(self._Dm, square=False)
         self.n_items = n_new
-        self.n_old = n_old
-        self.embedding_dim = embedding_dim
+        self.n_old = self._item_pairs = n_old
         self.n_all_pairs = n_new * n_old
-        self.p = self.n_all_pairs
-        self._weights, self._row_kept = (None if weights.source == W_NONE else weights), None
-        if weights.source == W_MATRIX:
-            self._weights, stats = _device_weights(weights, self._Dm, False, self.device)
-            self.p, self._row_kept = int(stats.kept), stats.row_kept
+        self._set_weights(weights, False)
         self.metric = metric if from_data else None
-        self.deviation_scale = deviation_scale
-        self.loss = loss
         self.constraint = _Free()
-        self.X = None
-        self.solve_stats = None
-        self.value = None
-        self.residual_norm = None
+        self._reset()
         self.row_status = None
-        self._work_buffer = None
-        self._rows_work_buffer = None
 
     def __str__(self):
         source = "data matrices, metric %s" % self.metric if self._A is not None else "distance matrix"
@@ -693,14 +669,6 @@ class DensePlacement(DenseMDE):
         """The average distortion of the new rows ``X`` [n_new, d] over all ``n_new * n_old`` pairs with the embedded
         rows (a 0-dim float32 tensor; differentiable w.r.t. ``X``)."""
         return _DenseDistortion.apply(self._embedding_arg(X), self)
-
-    def item_distortions(self, X=None):
-        """float32 [n_new]: for every new row the mean of the loss over its ``n_old`` pairs (with a weight matrix:
-        over the pairs it keeps).  Their mean is the average distortion."""
-        row_loss = self._evaluate(self._embedding_arg(X).detach())[2]
-        if self._row_kept is not None:
-            return (row_loss / self._row_kept.to(torch.float64)).to(torch.float32)
-        return (row_loss / float(self.n_old)).to(torch.float32)
 
     def initialization(self):
         """The default start [n_new, d]: every new row at the mean of the embedding vectors of its ``d + 1`` nearest

@@ -37,10 +37,7 @@ def check_solver(solver, name="solver"):
 
 
 def work_cross_rows(lib, n_q, n_c, d, slices, device):
-    nbytes = int(lib.mde_pair_loss_cross_rows_work_bytes(n_q, n_c, d, slices))
-    if nbytes < 0:
-        _lib.check(nbytes)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _lib.work_buffer(lib.mde_pair_loss_cross_rows_work_bytes, n_q, n_c, d, slices, device=device)
 
 
 def pair_loss_cross_rows(XQ, XC, spec, row_loss, row_grad, rows=None, Q=None, C=None, mode=0, Dm=None, d_scale=1.0,
