@@ -729,30 +729,14 @@ int mde_vec_stats(int64_t N, const float* g, const float* d, const float* x, dou
 typedef struct mde_lbfgs mde_lbfgs;
 int mde_lbfgs_create(int64_t N, int32_t history, mde_lbfgs** out);
 int mde_lbfgs_destroy(mde_lbfgs* o);
-int mde_lbfgs_reset(mde_lbfgs* o);                   /* lbfgs.py:378-388 */
-int32_t mde_lbfgs_count(const mde_lbfgs* o);
-/* Stage the candidate pair y = g - g_prev, s = t d in the spare slot, set g_prev <- g, and
- * compute every inner product the two-loop recursion needs.  dots (device doubles):
- *   [0] y.s  [1] y.y  [2] s.g  [3] y.g
- *   then for each stored pair j (oldest first): s_j.y*, y_j.y*, s*.y_j, s_j.g, y_j.g
- * `dots` must hold 4 + 5*history doubles.  g_prev may be NULL on the first call (nothing is
- * staged; only g_prev <- g is skipped too -- use mde_lbfgs_set_prev). */
-int mde_lbfgs_stage(mde_lbfgs* o, const float* g, float* g_prev, const float* d, float t,
-                    double* dots, double* work, void* stream);
-/* accept != 0: the staged pair becomes the newest pair (dropping the oldest when full). */
-int mde_lbfgs_commit(mde_lbfgs* o, int32_t accept);
-/* d_out = c_g g + sum_j (cs[j] s_j + cy[j] y_j) over stored pairs (oldest first); also
- * stats as mde_vec_stats(g, d_out, NULL).  cs, cy: HOST arrays of mde_lbfgs_count floats. */
-int mde_lbfgs_combine(mde_lbfgs* o, const float* g, float c_g, const float* cs, const float* cy,
-                      float* d_out, double* stats, double* work, void* stream);
-/* Device-driven variant: the whole direction update of one iteration without a host round trip
- * [ref: lbfgs.py:468-507].  mde_lbfgs_dev_reset empties the history (lbfgs.py:378-388);
- * mde_lbfgs_dev_step stages y = g - g_prev, s = t d (and sets g_prev <- g), accepts the pair iff
- * y.s > 1e-10 (dropping the oldest when the history is full), runs the two-loop recursion in
- * coefficient form on the device and writes the new direction to d_out (may alias d) and the
- * statistics of (g, d_out) to stats as mde_vec_stats(g, d_out, NULL) does.  ASYNC.  Do not mix with
- * the host-driven stage / commit / combine calls on one object.  mde_lbfgs_dev_info reads back the
- * number of stored pairs and whether the last pair was accepted (tests; SYNC). */
+/* The whole direction update of one iteration without a host round trip [ref: lbfgs.py:468-507]: the
+ * bookkeeping (slot order, Gram matrices of the stored pairs, coefficients) lives on the device.
+ * mde_lbfgs_dev_reset empties the history (lbfgs.py:378-388; call it once after mde_lbfgs_create);
+ * mde_lbfgs_dev_step stages y = g - g_prev, s = t d in the spare slot (and sets g_prev <- g), accepts
+ * the pair iff y.s > 1e-10 (dropping the oldest when the history is full), runs the two-loop recursion
+ * in coefficient form on the device and writes the new direction to d_out (may alias d) and the
+ * statistics of (g, d_out) to stats as mde_vec_stats(g, d_out, NULL) does.  ASYNC.  mde_lbfgs_dev_info
+ * reads back the number of stored pairs and whether the last pair was accepted (tests; SYNC). */
 int mde_lbfgs_dev_reset(mde_lbfgs* o, void* stream);
 int mde_lbfgs_dev_step(mde_lbfgs* o, const float* g, float* g_prev, const float* d, float t,
                        float* d_out, double* stats, double* work, void* stream);
@@ -760,7 +744,8 @@ int mde_lbfgs_dev_info(const mde_lbfgs* o, int32_t* count_host, int32_t* accepte
 /* The same step in two halves, for a solve whose vectors are SHARDED BY ROWS across ranks (every rank keeps the
  * history of its own rows: mde_lbfgs_create(N = its elements)) [ref: lbfgs.py:461-507, the loop being sharded]:
  * mde_lbfgs_dev_stage stages the pair and leaves the mde_lbfgs_dev_dots(o) = 4 + 5 * history inner products over the
- * rank's elements in work[0 ..) (device doubles); the caller sums them across the ranks IN PLACE (one small
+ * rank's elements in work[0 ..) (device doubles: [0] y.s [1] y.y [2] s.g [3] y.g, then for each stored pair j, oldest
+ * first: s_j.y, y_j.y, s.y_j, s_j.g, y_j.g); the caller sums them across the ranks IN PLACE (one small
  * all-reduce); mde_lbfgs_dev_finish takes the accept / drop-oldest decision and runs the two-loop recursion on the
  * sums (every rank: the same arithmetic on the same numbers) and writes the rank's elements of the new direction to
  * d_out and the statistics of (g, d_out) over ITS elements to stats (partial: see mde_rank_reduce).  In a world of

@@ -157,16 +157,10 @@ SYMBOLS = {
     "mde_vec_stats": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_lbfgs_create": (c_i32, [c_i64, c_i32, ctypes.POINTER(c_vp)]),
     "mde_lbfgs_destroy": (c_i32, [c_vp]),
-    "mde_lbfgs_reset": (c_i32, [c_vp]),
-    "mde_lbfgs_count": (c_i32, [c_vp]),
-    "mde_lbfgs_stage": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp]),
-    "mde_lbfgs_commit": (c_i32, [c_vp, c_i32]),
     "mde_lbfgs_dev_reset": (c_i32, [c_vp, c_vp]),
     "mde_lbfgs_dev_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mde_lbfgs_debug_knobs": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "mde_lbfgs_dev_info": (c_i32, [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp]),
-    "mde_lbfgs_combine": (c_i32, [c_vp, c_vp, c_f32, ctypes.POINTER(c_f32),
-                                  ctypes.POINTER(c_f32), c_vp, c_vp, c_vp, c_vp]),
     "mde_copy_to_host": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "mde_turn_enqueue": (c_i32, [c_vp, c_i32, c_f32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp]),
     "mde_turn_wait": (c_i32, [c_vp, c_i32, ctypes.c_double, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -3,8 +3,9 @@
 The ``Constraint`` protocol -- ``name / initialization / project_onto_constraint /
 project_onto_tangent_space`` with ``inplace`` flags -- is the reference's
 [ref: pymde/constraints.py:7-91]; the built-in constraints run on the HIP kernels of
-``csrc/mde_vec.hip`` (column-mean reduction, d x d Gram matrices -- f32 MFMA when d is a
-multiple of 32 --, d x d inverse square root, row-tile right-multiply).
+``csrc/mde_vec.hip`` (column-mean reduction, anchors) and ``csrc/mde_std.hip`` (d x d Gram
+matrices -- f32 MFMA when d is a multiple of 32 --, d x d inverse square root, row-tile
+right-multiply).
 
 Differences to the reference, both exact in exact arithmetic:
   * ``Standardized`` retracts with sqrt(n) Z C^{-1/2}, C = Z^T Z, instead of a thin SVD

@@ -3,8 +3,8 @@ recursion in coefficient form.
 
 Restates the algorithm of the reference's ``pymde/lbfgs.py`` (a fork of torch.optim.LBFGS)
 [ref: lbfgs.py:16-41 cubic interpolation, :44-253 strong Wolfe, :461-507 direction] as pure
-scalar code: every n*d-sized vector stays on the GPU (``csrc/mde_vec.hip``) and the host only
-sees the handful of inner products per step, so this module has no torch / GPU dependency
+scalar code: every n*d-sized vector stays on the GPU (``csrc/mde_lbfgs.hip``) and the host
+only sees the handful of inner products per step, so this module has no torch / GPU dependency
 and is unit-tested on the CPU.
 
 Direction in coefficient form.  With pairs (s_i, y_i), i = 0..m-1 oldest first,

@@ -4,7 +4,7 @@
 [ref: pymde/optim.py:69-184] (driven by ``MDE.embed``, problem.py:497-510) and
 ``SolveStats`` is the same record [ref: optim.py:11-66]; the implementation is not a
 torch.optim optimizer: iterate, trial point, gradient, direction and the L-BFGS history
-live in device buffers, every vector operation is a kernel of ``csrc/mde_vec.hip``, and the
+live in device buffers, every vector operation is a kernel of ``csrc/mde_vec.hip`` or ``csrc/mde_lbfgs.hip``, and the
 host receives ONE small read-back per objective evaluation (loss, g.d, |g|, finiteness) plus
 one per iteration (the inner products of the history update) -- the reference synchronises
 >= 12 times per iteration.
@@ -113,9 +113,6 @@ class _Engine(object):
         self._host_status_np = self.host_status.numpy()
         self._host_ptr = ctypes.c_void_p(self.host_raw.data_ptr() + 4 * b0)
         self._tail_ptr = ctypes.c_void_p(self.gtail.data_ptr() + 4 * self.N)
-        # the solve runs on the stream that is current now; its handle is looked up once
-        self._stream_obj = torch.cuda.current_stream(dev)
-        self._stream = ctypes.c_void_p(self._stream_obj.cuda_stream)
         # the solve runs on the stream that is current now; its handle is looked up once
         self._stream_obj = torch.cuda.current_stream(dev)
         self._stream = ctypes.c_void_p(self._stream_obj.cuda_stream)

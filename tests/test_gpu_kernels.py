@@ -85,6 +85,9 @@ def test_plan_matches_oracle_bit_exact(n, p, seed):
     flip = rng.random(p) < 0.5
     edges[flip] = edges[flip][:, ::-1]  # (j, i) orientation is legal too
     plan = EdgePlan(n, torch.tensor(edges, device=DEV))
+    from pymde_amd import _lib
+    lib = _lib.load()
+    assert (lib.mde_plan_n(plan.handle), lib.mde_plan_p(plan.handle)) == (n, p)  # the plan's own getters
     rowptr, nbr, eid = [t.cpu().numpy() for t in plan.csr()]
     w_rowptr, w_nbr, w_eid = oracle.plan_csr(n, edges)
     np.testing.assert_array_equal(rowptr, w_rowptr)

@@ -74,6 +74,43 @@ def test_ctypes_signatures_match_the_header_prototypes():
     assert seen == set(_lib.SYMBOLS)
 
 
+def test_every_bound_symbol_has_a_user():
+    """Every name of the ctypes table is referenced outside its own definition: as a whole word in the package
+    (_lib.py without the table itself), the tests, the Python tools, bench.py, or in the code of a csrc/ file on
+    another line than the one that defines it (comments and string literals are not code).  An entry point nobody
+    calls is dead weight in the header, the table and the library."""
+    import glob
+
+    def read(path):
+        with open(path, errors="replace") as f:
+            return f.read()
+
+    py = glob.glob(os.path.join(ROOT, "pymde_amd", "**", "*.py"), recursive=True)
+    py += glob.glob(os.path.join(ROOT, "tests", "**", "*.py"), recursive=True)
+    py += glob.glob(os.path.join(ROOT, "tools", "*.py")) + [os.path.join(ROOT, "bench.py")]
+    words = set()
+    for p in py:
+        text = read(p)
+        if os.path.basename(p) == "_lib.py":
+            text, cut = re.subn(r"^SYMBOLS = \{.*?^\}", "", text, flags=re.S | re.M)
+            assert cut == 1
+        words.update(re.findall(r"\bmde_[a-z0-9_]+\b", text))
+    for p in glob.glob(os.path.join(ROOT, "pymde_amd", "csrc", "*.h*")):  # (.h and .hip)
+        text = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group(0).count("\n"), read(p), flags=re.S)
+        for line in text.split("\n"):
+            line = re.sub(r'"(\\.|[^"\\])*"', '""', line)
+            line = re.sub(r"//.*", "", line)
+            for m in re.finditer(r"\bmde_[a-z0-9_]+\b", line):
+                # the defining line: nothing but a linkage specifier and the return type in front of the name
+                head = line[:m.start()].replace('extern ""', "")
+                defines = (re.fullmatch(r"\s*(const\s+)?(?!return\b|else\b)[A-Za-z_]\w*[\s\*]+", head) is not None
+                           and line[m.end():].lstrip().startswith("("))
+                if not defines:
+                    words.add(m.group(0))
+    unused = sorted(name for name in _lib.SYMBOLS if name not in words)
+    assert unused == [], "bound in _lib.SYMBOLS but used nowhere: " + ", ".join(unused)
+
+
 def test_mde_func_struct_layout_matches_header(tmp_path):
     """struct mde_func as gcc lays it out from include/mde_hip.h against the ctypes mirror (ABI 2: e0 / e1 at the end)."""
     import os
