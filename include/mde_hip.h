@@ -221,12 +221,24 @@ int mde_plan_expand_layout(const mde_plan* plan, int32_t layout, const float* in
  * [0] built (0 / 1), [1] embedding dimension, [2] rows (LDS slots) per row block, [3] row blocks, [4] column groups,
  * [5] chunks, [6] ring slots, [7] wave iterations, [8] half-edges in the ring streams, [9] padded entries,
  * [10] row blocks PERMUTED (rows dealt to the blocks by degree; every entry adds f / 2), [11] hub rows PEELED off to
- * the CSR hub kernel, [12] their half-edges, [13] their segments, [14], [15] reserved (0). */
+ * the CSR hub kernel, [12] their half-edges, [13] their segments, [14] loss band in vertices (below; 0: the entry
+ * whose row is the smaller vertex adds an edge's loss term), [15] reserved (0). */
 int mde_plan_ring_info(const mde_plan* plan, int64_t* info_host);
-/* Checks the lane-stable pairs of the LDS-ring layout on the device: out_host[0] = entries of a pair's second wave
- * iteration whose row the first iteration holds on another lane (0 in every layout the builder emits: the kernel reads
- * both accumulators of a pair before it writes either), [1] = rows held by both iterations of a pair, [2] = pairs.
- * All zero when no layout is built.  SYNC. */
+/* How the loss terms are spread over the LDS-ring layout, 8 HOST doubles.  Every edge has two entries (one per
+ * endpoint) and one of them adds the loss term.  With a loss band of W vertices (d = 2, full plans, rows not permuted)
+ * entry (row v, column u) adds it iff (v < u) xor ((v / W + u / W) odd), which gives every workgroup about half of its
+ * entries' terms; W = 0: iff v < u.  [0] W, [1] .. [3] blocks of four wave iterations in which no entry / every entry /
+ * some entries (per-lane test) add their term, [4], [5] smallest and largest fraction of a workgroup's entries that add
+ * their term, [6], [7] reserved (0).  All zero when no layout is built. */
+int mde_plan_ring_loss_balance(const mde_plan* plan, double* out_host);
+/* Checks the LDS-ring layout on the device, 8 HOST int64.  The lane-stable pairs: out_host[0] = entries of a pair's
+ * second wave iteration whose row the first iteration holds on another lane (0 in every layout the builder emits: the
+ * kernel reads both accumulators of a pair before it writes either), [1] = rows held by both iterations of a pair,
+ * [2] = pairs.  Who adds an edge's loss term (layouts whose rows are not permuted; hub rows included): [3] = edges
+ * whose term is not added exactly once over their two entries, as the kernels decide it (0 in every layout the builder
+ * emits), [4] = entries whose flag in the packed word (d = 2) disagrees with the rule recomputed from row and column
+ * (0 likewise), [5] = edges with both entries in this plan, [6], [7] reserved (0).  All zero when no layout is built.
+ * SYNC. */
 int mde_plan_ring_check(const mde_plan* plan, int64_t* out_host, void* stream);
 /* Processing order of the plan's rows for the general-d kernel (d = 5 .. 512; round 6).  The reference evaluates
  * the edges in the caller's order whatever the numbering of the items [ref: pymde/average_distortion.py:62-106]; here

@@ -60,6 +60,7 @@ SYMBOLS = {
     "mde_plan_layout": (c_i32, [c_vp, c_i32, c_vp]),
     "mde_plan_layout_half_edges": (c_i64, [c_vp, c_i32]),
     "mde_plan_ring_info": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
+    "mde_plan_ring_loss_balance": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_double)]),
     "mde_plan_ring_check": (c_i32, [c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_plan_row_order": (c_i32, [c_vp, c_i32, c_vp, ctypes.POINTER(ctypes.c_double)]),
     "mde_plan_function_hint": (c_i32, [c_vp, c_i32, c_i32]),

@@ -119,26 +119,36 @@ class EdgePlan(object):
         return out if nv.value > 0 else None
 
     def ring_info(self):
-        """The LDS-ring layout of the plan as a dict (``mde_plan_ring_info``); ``built`` is False before the first
-        evaluation at a dimension that takes it."""
+        """The LDS-ring layout of the plan as a dict (``mde_plan_ring_info``, ``mde_plan_ring_loss_balance``); ``built``
+        is False before the first evaluation at a dimension that takes it.  ``loss_band``: width in vertices of the bands
+        between which the rule for who adds an edge's loss term flips (0: the smaller endpoint does); ``class_blocks``:
+        blocks of four wave iterations in which no / every / some entries add their term; ``loss_share_min`` /
+        ``loss_share_max``: smallest and largest fraction of a workgroup's entries that add their term."""
         lib = _lib.load()
         info = (ctypes.c_int64 * 16)()
         _lib.check(lib.mde_plan_ring_info(self._handle, info))
         names = ("built", "d", "rows_per_block", "row_blocks", "col_groups", "chunks", "ring_slots", "iterations",
-                 "ring_half_edges", "padded_entries", "permuted", "hub_rows", "hub_half_edges", "hub_segments")
+                 "ring_half_edges", "padded_entries", "permuted", "hub_rows", "hub_half_edges", "hub_segments", "loss_band")
         out = {k: int(info[i]) for i, k in enumerate(names)}
         out["built"], out["permuted"] = bool(out["built"]), bool(out["permuted"])
+        bal = (ctypes.c_double * 8)()
+        _lib.check(lib.mde_plan_ring_loss_balance(self._handle, bal))
+        out["class_blocks"] = tuple(int(bal[i]) for i in (1, 2, 3))
+        out["loss_share_min"], out["loss_share_max"] = float(bal[4]), float(bal[5])
         return out
 
     def ring_check(self):
-        """Device check of the LDS-ring layout's lane-stable pairs (``mde_plan_ring_check``): ``split`` entries whose
+        """Device check of the LDS-ring layout (``mde_plan_ring_check``).  Lane-stable pairs: ``split`` entries whose
         row the other iteration of their pair holds on another lane (always 0), ``shared`` rows held by both
-        iterations of a pair, ``pairs`` checked."""
+        iterations of a pair, ``pairs`` checked.  Loss terms (layouts whose rows are not permuted): ``loss_bad`` edges
+        whose term is not added exactly once (always 0), ``loss_flag_bad`` entries whose flag in the packed word
+        disagrees with the rule (always 0), ``loss_edges`` edges with both entries in this plan."""
         lib = _lib.load()
-        out = (ctypes.c_int64 * 3)()
+        out = (ctypes.c_int64 * 8)()
         with torch.cuda.device(self.device):
             _lib.check(lib.mde_plan_ring_check(self._handle, out, _lib.stream_ptr(self.device)))
-        return {"split": int(out[0]), "shared": int(out[1]), "pairs": int(out[2])}
+        return {"split": int(out[0]), "shared": int(out[1]), "pairs": int(out[2]), "loss_bad": int(out[3]),
+                "loss_flag_bad": int(out[4]), "loss_edges": int(out[5])}
 
     def row_order(self, mode=1):
         """Build (mode 1: keep if it helps, 2: keep regardless) or drop (0) the breadth-first processing order of the

@@ -32,6 +32,9 @@ struct mde_ring_layout {
   //    MDE_HUB_SEG positions, behind the ring kernel on the same stream (one writer per row, fixed order).
   int32_t* slot_row = nullptr;
   int count_all = 0;            // 1: every entry adds f / 2 (permuted layouts); 0: the smaller endpoint adds f
+  int loss_band = 0;            // W of ring_counts (mde_ring.h), in vertices; 0: the smaller endpoint adds f
+  int64_t class_blocks[3] = {0, 0, 0};             // blocks of four iterations by loss class (0 none, 1 all, 2 per lane)
+  double loss_share_min = 0.0, loss_share_max = 0.0;  // smallest / largest fraction of a workgroup's entries that add their loss term
   int n_hub_rows = 0, n_hub_segs = 0;
   int64_t hub_half_edges = 0;
   int32_t* hub_rows = nullptr;  // [n_hub_rows] local row ids, ascending

@@ -103,16 +103,30 @@ __host__ __device__ constexpr int ring_max_span(int S) {
 //       iterations around the diagonal)
 //   [3] bits 1:0 (first iteration of a block of four only): loss class of the BLOCK -- 0 / 1 when every
 //       non-empty iteration of the block has that class, else 2 (the kernel branches once per block);
-//       bit 2: the iteration has padding lanes; bits 15:8: its number of entries
+//       bit 2: the iteration has padding lanes; bits 15:8: its number of entries; bits 23:16: how many of
+//       them add their loss term here
 #define MDE_RING_HW 4
 #define MDE_RING_H3_PAD 4u
 
 // Packed word of an entry (absolute LDS byte addresses, fixed when the layout is built):
 //   d = 2:  [2:0] parameter codebook index (0 when the parameters stream as fp32)
 //           [15:3] x_v address / 8 (the accumulator sits GR_OFF above it)   [30:16] x_u address / 8
+//           [31] this entry adds the edge's loss term (ring_counts; the kernel's per-lane test in class-2 blocks)
 //   else:   [15:2] x_v address / 4, [1:0] codebook index (d = 3 only)       [31:16] x_u address / 4
 __host__ __device__ inline uint32_t ring_pack_word(int d, uint32_t rowaddr, uint32_t coladdr) {
   return d == 2 ? (rowaddr | ((coladdr >> 3) << 16)) : (rowaddr | ((coladdr >> 2) << 16));
+}
+
+#define MDE_RING_COUNTS_BIT 0x80000000u
+
+// Which of an edge's two entries adds its loss term (layouts that are not permuted): entry (row v, column u) does iff
+// ring_counts(v, u, W).  W = 0: the smaller vertex.  W > 0 (mde_ring_layout::loss_band): the vertex order is cut into
+// bands of W vertices and the rule flips wherever the two bands' numbers add up to an odd one -- antisymmetric in
+// (v, u), so still exactly one of the two entries, and every (row block, column group) workgroup adds about half of
+// its entries' terms instead of all or none of them.
+__host__ __device__ inline bool ring_counts(uint32_t v, uint32_t u, uint32_t W) {
+  const bool lower = v < u;
+  return W ? (lower != (((v / W + u / W) & 1u) != 0u)) : lower;
 }
 
 // ---------------------------------------------------------------- launching

@@ -539,7 +539,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
                                                          const int32_t* __restrict__ nbr,
                                                          const int32_t* __restrict__ eid, int R, int Q, int C, int S,
                                                          int ring_off, int JB, int d, int row_lo, int place, int count_all,
-                                                         uint32_t* __restrict__ packed,
+                                                         int loss_band, uint32_t* __restrict__ packed,
                                                          int32_t* __restrict__ peid, uint32_t* __restrict__ hdr) {
   __shared__ uint8_t s_taken[MDE_BLOCK / 64][64], s_free[MDE_BLOCK / 64][64];
   __shared__ uint32_t s_prow[MDE_BLOCK / 64][64];  // the rows of a pair's first iteration, by lane
@@ -626,9 +626,9 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
     const unsigned long long mvm = __ballot(moved);
     const int nmoved = __popcll(mvm);
     if (moved) l = s_free[wv][__popcll(mvm & ((1ull << lane) - 1ull))];
-    // whose loss terms: the entry whose row is the smaller vertex of the edge (grow is the local row there); a
-    // permuted layout (grow is a slot) adds every entry's with weight 1/2
-    const bool counts = act && (count_all || (uint32_t)(row_lo + grow) < col);
+    // whose loss terms: one of the edge's two entries by ring_counts (grow is the local row there: the smaller vertex,
+    // flipped between bands of loss_band vertices); a permuted layout (grow is a slot) adds every entry's with weight 1/2
+    const bool counts = act && (count_all || ring_counts((uint32_t)(row_lo + grow), col, (uint32_t)loss_band));
     const int ncount = __popcll(__ballot(counts));
     const uint32_t lclass = ncount == 0 ? 0u : (ncount == cnt ? 1u : 2u);
     // chunk window of the iteration: the oldest chunk its stream still needs (waiting entries
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
     // element (iteration it, lane l) of a stream lives at ((it / 4) * 64 + l) * 4 + it % 4
     const size_t base = ((size_t)(it >> 2) * 64) * 4 + (size_t)(it & 3);
     if (act) {
-      packed[base + (size_t)l * 4] = ring_pack_word(d, rowaddr, ring);
+      packed[base + (size_t)l * 4] = ring_pack_word(d, rowaddr, ring) | ((d == 2 && counts) ? MDE_RING_COUNTS_BIT : 0u);
       peid[base + (size_t)l * 4] = eid[q];
     } else if (valid) {
       // padding: a dummy row slot of the lane's own bank class, a resident column
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pack(int64_t nit, int nseg, 
       hdr[MDE_RING_HW * it] = m;
       hdr[MDE_RING_HW * it + 1] = need;
       hdr[MDE_RING_HW * it + 2] = lclass;
-      hdr[MDE_RING_HW * it + 3] = (cnt < 64 ? MDE_RING_H3_PAD : 0u) | ((uint32_t)cnt << 8);
+      hdr[MDE_RING_HW * it + 3] = (cnt < 64 ? MDE_RING_H3_PAD : 0u) | ((uint32_t)cnt << 8) | ((uint32_t)ncount << 16);
     }
     __syncthreads();
   }
@@ -704,6 +704,38 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_stats(int64_t nit, const uin
     atomicAdd(&stats[0], a);
     atomicAdd(&stats[1], b);
     atomicAdd(&stats[2], c);
+  }
+}
+
+// How the loss terms are spread (mde_plan_ring_loss_balance).  One wave per workgroup: wg[2 * g] = entries of its
+// streams, wg[2 * g + 1] = those that add their loss term (header word 3); cls[c] += blocks of four iterations of
+// loss class c.
+__global__ __launch_bounds__(64) void k_ring_loss_stats(const int32_t* __restrict__ wave_iter, const uint32_t* __restrict__ hdr,
+                                                        unsigned long long* __restrict__ wg, unsigned long long* __restrict__ cls) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const int64_t i0 = wave_iter[(size_t)g * MDE_RING_NCW], i1 = wave_iter[(size_t)(g + 1) * MDE_RING_NCW];
+  unsigned long long ent = 0, cnt = 0, c0 = 0, c1 = 0, c2 = 0;
+  for (int64_t i = i0 + lane; i < i1; i += 64) {
+    const uint32_t h3 = hdr[MDE_RING_HW * i + 3];
+    ent += (h3 >> 8) & 0xffu;
+    cnt += (h3 >> 16) & 0xffu;
+    if ((i & 3) == 0) {  // (streams start on multiples of 4)
+      c0 += (h3 & 3u) == 0u;
+      c1 += (h3 & 3u) == 1u;
+      c2 += (h3 & 3u) == 2u;
+    }
+  }
+  ent = mde_wave_sum(ent);
+  cnt = mde_wave_sum(cnt);
+  c0 = mde_wave_sum(c0);
+  c1 = mde_wave_sum(c1);
+  c2 = mde_wave_sum(c2);
+  if (lane == 0) {
+    wg[2 * g] = ent;
+    wg[2 * g + 1] = cnt;
+    atomicAdd(&cls[0], c0);
+    atomicAdd(&cls[1], c1);
+    atomicAdd(&cls[2], c2);
   }
 }
 
@@ -1429,11 +1461,26 @@ static int build_ring(mde_plan* plan, int d, hipStream_t st) {
                        z.Q, z.NC, d, cap, 0, nullptr, iter_base, it_ent, it_cnt, it_m, flag_rows, nullptr);
     e = hipGetLastError();
   }
+  // Who adds an edge's loss term (ring_counts, mde_ring.h).  "The smaller vertex" puts the loss arithmetic on one
+  // corner of the (row block, column group) grid: the workgroups of the low row blocks' upper column group add a
+  // term on every entry, those of the high row blocks' lower group on none, and a launch of one round ends with its
+  // slowest workgroup.  Bands of W vertices with the rule flipped between bands of unlike parity give every workgroup
+  // about half: ~8 bands per column group, W a multiple of the block height (a wave's rows lie in one band, so the
+  // iterations stay all-or-none except where a chunk window crosses a band's edge).  d = 2 only (the per-lane test
+  // of those iterations is bit 31 of the packed word; d = 3 has no spare bit), full plans only (the shards of a
+  // sharded problem choose R independently and must agree on the rule), not for permuted layouts (every entry
+  // adds f / 2 there).  MDE_RING_LOSS_BAND: the band in row blocks, 0 = the smaller vertex everywhere.
+  int loss_band = 0;
+  if (d == 2 && !rp.permuted && plan->row_lo == 0 && nloc == plan->n) {
+    int64_t wb = std::max<int64_t>(1, (int64_t)z.NRB / (8 * (int64_t)z.Q));
+    if (getenv("MDE_RING_LOSS_BAND")) wb = std::max(0, atoi(getenv("MDE_RING_LOSS_BAND")));
+    loss_band = (int)std::min<int64_t>(wb * (int64_t)z.R, (int64_t)1 << 30);
+  }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_ring_pack, dim3(mde_grid((int64_t)total_iters * 64, MDE_BLOCK, 8192)), dim3(MDE_BLOCK), 0, st,
                        (int64_t)total_iters, nseg, iter_base, single ? cap_base : nullptr, it_ent, it_cnt, it_m, keys2, vals2, hrow,
                        plan->nbr, plan->eid, z.R, z.Q, z.C, z.S, z.ring_off, z.JB, d, (int)plan->row_lo, place, rp.permuted ? 1 : 0,
-                       packed, peid, hdr);
+                       loss_band, packed, peid, hdr);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // (cap_base is read by the pack kernel)
@@ -1443,6 +1490,23 @@ static int build_ring(mde_plan* plan, int d, hipStream_t st) {
                      (int64_t)(total_iters / 4), hdr);
   RB(hipGetLastError());
   RB(hipStreamSynchronize(st));
+  // how the loss terms fell on the workgroups (mde_plan_ring_loss_balance)
+  const int nwg = z.NRB * z.Q;
+  std::vector<unsigned long long> lstat((size_t)2 * nwg + 3, 0ull);
+  {
+    unsigned long long* dl = nullptr;
+    const size_t lb = lstat.size() * sizeof(unsigned long long);
+    e = hipMalloc(&dl, lb);
+    if (e == hipSuccess) e = hipMemsetAsync(dl, 0, lb, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_ring_loss_stats, dim3(nwg), dim3(64), 0, st, iter_base, hdr, dl, dl + 2 * (size_t)nwg);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(lstat.data(), dl, lb, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (dl) (void)hipFree(dl);
+    if (e != hipSuccess) return fail(e, "ring layout: loss statistics");
+  }
   if (getenv("MDE_RING_STATS")) {
     unsigned long long* dstat = reinterpret_cast<unsigned long long*>(iters);  // scratch, >= 3 words
     unsigned long long hstat[3] = {0, 0, 0};
@@ -1540,6 +1604,19 @@ static int build_ring(mde_plan* plan, int d, hipStream_t st) {
   L.partial = partial;
   L.slot_row = slot_row;
   L.count_all = rp.permuted ? 1 : 0;
+  L.loss_band = loss_band;
+  {
+    double lo = 2.0, hi = -1.0;
+    for (int g = 0; g < nwg; ++g) {
+      if (lstat[2 * (size_t)g] == 0) continue;
+      const double sh = (double)lstat[2 * (size_t)g + 1] / (double)lstat[2 * (size_t)g];
+      lo = std::min(lo, sh);
+      hi = std::max(hi, sh);
+    }
+    L.loss_share_min = hi < 0.0 ? 0.0 : lo;
+    L.loss_share_max = hi < 0.0 ? 0.0 : hi;
+    for (int c = 0; c < 3; ++c) L.class_blocks[c] = (int64_t)lstat[2 * (size_t)nwg + c];
+  }
   L.n_hub_rows = (int)rp.hub_rows.size();
   L.n_hub_segs = (int)(rp.hub_seg.size() / 4);
   L.hub_half_edges = rp.hub_half_edges;
@@ -1910,6 +1987,19 @@ extern "C" int mde_plan_ring_info(const mde_plan* plan, int64_t* info) {
   info[11] = L.n_hub_rows;
   info[12] = L.hub_half_edges;
   info[13] = L.n_hub_segs;
+  info[14] = L.loss_band;
+  return MDE_OK;
+}
+
+extern "C" int mde_plan_ring_loss_balance(const mde_plan* plan, double* out) {
+  if (!plan || !out) return MDE_E_INVALID;
+  const mde_ring_layout& L = plan->ring;
+  for (int i = 0; i < 8; ++i) out[i] = 0.0;
+  if (!L.packed) return MDE_OK;
+  out[0] = (double)L.loss_band;
+  for (int c = 0; c < 3; ++c) out[1 + c] = (double)L.class_blocks[c];
+  out[4] = L.loss_share_min;
+  out[5] = L.loss_share_max;
   return MDE_OK;
 }
 
@@ -1941,29 +2031,130 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_pair_check(int64_t npairs, c
   }
 }
 
+// Who adds an edge's loss term, as the KERNEL will decide it (layouts that are not permuted).  One wave per iteration:
+// every real entry adds 0x10000 (seen) + 1 (when its term is added here: block class 1, or class 2 and the per-lane
+// test -- bit 31 of the packed word at d = 2, the rule recomputed from the addresses otherwise) to its edge's word of
+// `hist`.  out[4] += entries whose bit 31 (d = 2) disagrees with ring_counts recomputed from (row, column), padding
+// entries with the bit set included.
+__global__ __launch_bounds__(MDE_BLOCK) void k_ring_loss_mark(int64_t nit, int nseg, const int32_t* __restrict__ wave_iter,
+                                                              const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ packed,
+                                                              const int32_t* __restrict__ peid, int d, int R, int Q, int C, int S,
+                                                              int ring_off, int row_lo, int loss_band, int64_t p,
+                                                              uint32_t* __restrict__ hist, unsigned long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = ((int64_t)gridDim.x * MDE_BLOCK) >> 6;
+  const uint32_t cbytes = (uint32_t)C * 4u * (uint32_t)d;
+  unsigned long long mism = 0;
+  for (int64_t it = ((int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x) >> 6; it < nit; it += nw) {
+    int lo = 0, hi = nseg;  // wave_iter[lo] <= it < wave_iter[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if ((int64_t)wave_iter[mid] <= it) lo = mid; else hi = mid;
+    }
+    const int rb = (lo / MDE_RING_NCW) / Q;
+    const size_t idx = ((size_t)(it >> 2) * 64 + (size_t)lane) * 4 + (size_t)(it & 3);
+    const uint32_t w = packed[idx];
+    const int32_t e = peid[idx];
+    const bool bit = d == 2 && (w & MDE_RING_COUNTS_BIT) != 0u;
+    if (e < 0 || (int64_t)e >= p) {
+      mism += bit ? 1u : 0u;
+      continue;
+    }
+    const uint32_t hm = hdr[MDE_RING_HW * it];
+    const uint32_t bcls = hdr[MDE_RING_HW * (it & ~(int64_t)3) + 3] & 3u;
+    const uint32_t rowaddr = d == 2 ? (w & 0xfff8u) : (w & 0xfffcu);
+    const uint32_t coladdr = d == 2 ? ((w >> 13) & 0x3fff8u) : ((w >> 14) & 0x3fffcu);
+    const uint32_t off = coladdr - (uint32_t)ring_off;
+    const uint32_t slot = off / cbytes, cidx = (off - slot * cbytes) / (4u * (uint32_t)d);
+    const uint32_t ms = hm % (uint32_t)S;
+    const uint32_t j = hm + (slot >= ms ? slot - ms : slot + (uint32_t)S - ms);
+    const uint32_t u = j * (uint32_t)C + cidx;
+    const uint32_t v = (uint32_t)row_lo + (uint32_t)rb * (uint32_t)R + rowaddr / (4u * (uint32_t)d);
+    const bool rule = ring_counts(v, u, (uint32_t)loss_band);
+    if (d == 2 && bit != rule) ++mism;
+    const bool here = bcls == 0u ? false : (bcls == 1u ? true : (d == 2 ? bit : rule));
+    atomicAdd(&hist[e], 0x10000u + (here ? 1u : 0u));
+  }
+  mism = mde_wave_sum(mism);
+  if (lane == 0 && mism) atomicAdd(&out[4], mism);
+}
+
+// ... and the peeled hub rows' half-edges (k_hub_rows decides with ring_counts): one workgroup per segment
+__global__ __launch_bounds__(MDE_BLOCK) void k_ring_loss_mark_hub(const int32_t* __restrict__ hub_rows, const int32_t* __restrict__ hub_seg,
+                                                                  int row_lo, const int32_t* __restrict__ nbr,
+                                                                  const int32_t* __restrict__ eid, int loss_band, int64_t p,
+                                                                  uint32_t* __restrict__ hist) {
+  const int sgi = blockIdx.x;
+  const int hi = hub_seg[4 * sgi], beg = hub_seg[4 * sgi + 1], end = hub_seg[4 * sgi + 2];
+  const uint32_t v = (uint32_t)row_lo + (uint32_t)hub_rows[hi];
+  for (int h = beg + (int)threadIdx.x; h < end; h += MDE_BLOCK) {
+    const int32_t e = eid[h];
+    if (e < 0 || (int64_t)e >= p) continue;
+    atomicAdd(&hist[e], 0x10000u + (ring_counts(v, (uint32_t)nbr[h], (uint32_t)loss_band) ? 1u : 0u));
+  }
+}
+
+// out[3] += edges whose loss term is not added exactly once (of the edges with both entries in this plan; an edge with
+// one entry here -- a sharded plan -- may add at most one), out[5] += edges with both entries here
+__global__ __launch_bounds__(MDE_BLOCK) void k_ring_loss_count(int64_t p, const uint32_t* __restrict__ hist,
+                                                               unsigned long long* __restrict__ out) {
+  unsigned long long bad = 0, both = 0;
+  for (int64_t e = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; e < p; e += (int64_t)gridDim.x * MDE_BLOCK) {
+    const uint32_t seen = hist[e] >> 16, c = hist[e] & 0xffffu;
+    both += seen == 2u;
+    bad += seen > 2u || (seen == 2u && c != 1u) || (seen == 1u && c > 1u);
+  }
+  bad = mde_wave_sum(bad);
+  both = mde_wave_sum(both);
+  if ((threadIdx.x & 63) == 0) {
+    if (bad) atomicAdd(&out[3], bad);
+    if (both) atomicAdd(&out[5], both);
+  }
+}
+
 extern "C" int mde_plan_ring_check(const mde_plan* plan, int64_t* out_host, void* stream) {
   if (!plan || !out_host) return MDE_E_INVALID;
   const mde_ring_layout& L = plan->ring;
-  for (int i = 0; i < 3; ++i) out_host[i] = 0;
+  for (int i = 0; i < 8; ++i) out_host[i] = 0;
   if (!L.packed || L.n_iters == 0) return MDE_OK;
   hipStream_t st = mde_stream(stream);
   unsigned long long* dout = nullptr;
-  hipError_t e = hipMalloc(&dout, 3 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemsetAsync(dout, 0, 3 * sizeof(unsigned long long), st);
+  uint32_t* hist = nullptr;
+  const bool loss_check = !L.count_all && plan->p > 0;
+  hipError_t e = hipMalloc(&dout, 8 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemsetAsync(dout, 0, 8 * sizeof(unsigned long long), st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_ring_pair_check, dim3(mde_grid(L.n_iters / 2 * 64, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st,
                        L.n_iters / 2, L.packed, L.d, L.rows_per_block, dout);
     e = hipGetLastError();
   }
-  unsigned long long h[3] = {0, 0, 0};
+  if (e == hipSuccess && loss_check) e = hipMalloc(&hist, (size_t)plan->p * sizeof(uint32_t));
+  if (e == hipSuccess && loss_check) e = hipMemsetAsync(hist, 0, (size_t)plan->p * sizeof(uint32_t), st);
+  if (e == hipSuccess && loss_check) {
+    hipLaunchKernelGGL(k_ring_loss_mark, dim3(mde_grid(L.n_iters * 64, MDE_BLOCK, 8192)), dim3(MDE_BLOCK), 0, st, L.n_iters,
+                       L.n_row_blocks * L.col_groups * MDE_RING_NCW, L.wave_iter, L.hdr, L.packed, L.eid, L.d, L.rows_per_block,
+                       L.col_groups, L.chunk_cols, L.slots, L.ring_off, (int)plan->row_lo, L.loss_band, plan->p, hist, dout);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && loss_check && L.n_hub_segs > 0) {
+    hipLaunchKernelGGL(k_ring_loss_mark_hub, dim3(L.n_hub_segs), dim3(MDE_BLOCK), 0, st, L.hub_rows, L.hub_seg, (int)plan->row_lo,
+                       plan->nbr, plan->eid, L.loss_band, plan->p, hist);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && loss_check) {
+    hipLaunchKernelGGL(k_ring_loss_count, dim3(mde_grid(plan->p, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, plan->p, hist, dout);
+    e = hipGetLastError();
+  }
+  unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (e == hipSuccess) e = hipMemcpyAsync(h, dout, sizeof(h), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (dout) (void)hipFree(dout);
+  if (hist) (void)hipFree(hist);
   if (e != hipSuccess) {
     mde_set_error("mde_plan_ring_check: %s", hipGetErrorString(e));
     return MDE_E_HIP;
   }
-  for (int i = 0; i < 3; ++i) out_host[i] = (int64_t)h[i];
+  for (int i = 0; i < 8; ++i) out_host[i] = (int64_t)h[i];
   return MDE_OK;
 }
 
@@ -1988,14 +2179,14 @@ extern "C" int mde_plan_expand_layout(const mde_plan* plan, int32_t layout, cons
 // the ring-order streams do not hold these entries), sum g (x_v - x_u) and the loss terms over the segment in a fixed
 // order (lane-strided partial sums, wave butterflies, waves in order; double).  k_hub_finish adds a row's segments in
 // order, writes the gradient row (overwriting the zeros the ring kernel's epilogue left there) and adds the hub rows'
-// loss to the ring kernel's: same stream, behind it.  count_all: the layout's rule for who adds an edge's loss term.
+// loss to the ring kernel's: same stream, behind it.  count_all, loss_band: the layout's rule for who adds an edge's loss term.
 template <int D>
 __global__ __launch_bounds__(MDE_BLOCK) void k_hub_rows(const int32_t* __restrict__ hub_rows, const int32_t* __restrict__ hub_seg,
                                                         int row_lo, const int32_t* __restrict__ nbr,
                                                         const int32_t* __restrict__ eid, const float* __restrict__ e0,
                                                         const float* __restrict__ e1, int e0_scalar, int e1_scalar,
                                                         const float* __restrict__ X, FnRuntime fn, float inv_p, int count_all,
-                                                        double* __restrict__ partial) {
+                                                        int loss_band, double* __restrict__ partial) {
   __shared__ double smem[8];
   const int sgi = blockIdx.x;
   const int hi = hub_seg[4 * sgi], beg = hub_seg[4 * sgi + 1], end = hub_seg[4 * sgi + 2];
@@ -2021,7 +2212,8 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_hub_rows(const int32_t* __restric
     float f, gd;
     fn.eval(ss, p0, p1, f, gd);
     const float g = mde_fix_g(gd * inv_p);
-    if (count_all || v < (int64_t)u) loss += (double)f;
+    // (the twin entry of this half-edge sits in a ring stream: the same rule on both sides)
+    if (count_all || ring_counts((uint32_t)v, (uint32_t)u, (uint32_t)loss_band)) loss += (double)f;
 #pragma unroll
     for (int c = 0; c < D; ++c) acc[c] += (double)(g * diff[c]);
   }
@@ -2079,7 +2271,7 @@ static int hub_launch_d(const mde_plan* plan, const float* X, const mde_func* f,
   const mde_ring_layout& L = plan->ring;
   FnRuntime fn{ring_func_args(f)};
   hipLaunchKernelGGL(k_hub_rows<D>, dim3(L.n_hub_segs), dim3(MDE_BLOCK), 0, st, L.hub_rows, L.hub_seg, (int)plan->row_lo, plan->nbr,
-                     plan->eid, e0, e1, e0_scalar, e1_scalar, X, fn, inv_p, L.count_all, L.hub_partial);
+                     plan->eid, e0, e1, e0_scalar, e1_scalar, X, fn, inv_p, L.count_all, L.loss_band, L.hub_partial);
   MDE_LAUNCH_CHECK();
   const int nb = L.n_hub_rows + 1;
   // (the ring kernel's rule: the smaller endpoint adds f -> 2 x the caller's half-weight; count_all: every entry f / 2)

@@ -529,15 +529,21 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
       };
       // 4 x the value index of iteration q of a block (byte q of the block's index word)
       auto bx4 = [&](uint32_t bw, int q) __attribute__((always_inline)) { return BX ? ((bw >> (8 * q)) & 0xffu) << 2 : 0u; };
-      // this entry adds the loss term iff its row is the smaller vertex (blocks around the diagonal)
+      // does this entry add the loss term?  (class-2 blocks only.)  d = 2: the layout builder left the answer in bit 31
+      // of the packed word (ring_counts, mde_ring.h: the blocks where a chunk window crosses the edge of a loss band,
+      // and those around the diagonal).  Otherwise: iff its row is the smaller vertex, from the addresses.
       auto counts_here = [&](uint32_t w, uint32_t hm) __attribute__((always_inline)) {
-        const uint32_t off = col_of(w) - (uint32_t)ring_off;
-        const uint32_t slot = off / (uint32_t)CBYTES, cidx = (off - slot * (uint32_t)CBYTES) / (4u * (uint32_t)D);
-        const uint32_t ms = hm % (uint32_t)S;
-        const uint32_t j = hm + (slot >= ms ? slot - ms : slot + (uint32_t)S - ms);
-        const uint32_t u = j * (uint32_t)C + cidx;
-        const uint32_t vv = (uint32_t)(row_lo + r0) + row_of(w) / (4u * (uint32_t)D);
-        return vv < u;
+        if constexpr (D == 2) {
+          return (int)w < 0;
+        } else {
+          const uint32_t off = col_of(w) - (uint32_t)ring_off;
+          const uint32_t slot = off / (uint32_t)CBYTES, cidx = (off - slot * (uint32_t)CBYTES) / (4u * (uint32_t)D);
+          const uint32_t ms = hm % (uint32_t)S;
+          const uint32_t j = hm + (slot >= ms ? slot - ms : slot + (uint32_t)S - ms);
+          const uint32_t u = j * (uint32_t)C + cidx;
+          const uint32_t vv = (uint32_t)(row_lo + r0) + row_of(w) / (4u * (uint32_t)D);
+          return vv < u;
+        }
       };
       // evaluate the entry and add its gradient term to the row's accumulator (read earlier).  LC is
       // the loss class of the BLOCK (compile time: no branch per iteration): 0 no entry adds its loss
@@ -722,7 +728,7 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
           prefetch_landed();
           const float p1a = a1_arr ? a1[((size_t)((ib >> 2) + b) * 64 + lane) * 4 + q] : a1s;
           const float p1b = a1_arr ? a1[((size_t)((ib >> 2) + b) * 64 + lane) * 4 + q + 1] : a1s;
-          const bool lc2 = decltype(lc_tag)::value == 2;
+          const bool lc2 = decltype(lc_tag)::value == 2 && D != 2;  // (d = 2 needs no header word for the test)
           const uint32_t hma = lc2 ? (uint32_t)__builtin_amdgcn_readlane((int)hv[u], 4 * q) : 0u;
           const uint32_t hmb = lc2 ? (uint32_t)__builtin_amdgcn_readlane((int)hv[u], 4 * q + 4) : 0u;
           finish(lc_tag, pq[u][q], xa, acc, p1a, hma);
