@@ -131,7 +131,7 @@ def test_csr_kernels(monkeypatch, dim, flat, c):
 
 # ------------------------------------------------------------------------------------ 3. wide kernels, d = 8
 # The probe axis is the last coordinate (the second float4 of a row).  Default: the pipelined k_fused_wide4p;
-# MDE_WIDE_P=0: k_fused_wide4.  Log1p(1.5) is FnSingle<LOG1P, 2> here, everything else FnRuntime.
+# MDE_WIDE_P=0: the 16-byte form of k_fused_wide.  Log1p(1.5) is FnSingle<LOG1P, 2> here, everything else FnRuntime.
 @pytest.mark.parametrize("c", CASES, ids=IDS)
 def test_wide_kernel(monkeypatch, c):
     monkeypatch.delenv("MDE_WIDE_P", raising=False)

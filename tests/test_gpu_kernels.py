@@ -1,5 +1,7 @@
 """Parity of the HIP path (through the C ABI) with the oracle and the reference's golden
 vectors -- plan, fused kernel, edge-order evaluators, constraints.  Needs an MI355X."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -1101,7 +1103,7 @@ def _band_graph(rng, n, deg, window, shuffle):
                                127, 128, 129, 200, 255, 256, 257, 388, 511, 512])
 def test_pipelined_wide_kernel_on_ragged_graphs(d, monkeypatch):
     """k_fused_wide4p (every d = 5 .. 512: 1 .. 32 lanes x 2 .. 4 float4s per half-edge at any float of a row -- 4-byte aligned 16-byte accesses --, the row's last column shifted back and masked where d is not a multiple of 4): empty rows, rows of one to three half-edges, a hub,
-    odd and even step counts -- against the oracle, against the unpipelined kernel (MDE_WIDE_P=0), three runs bitwise."""
+    odd and even step counts -- against the oracle, against the unpipelined kernel (k_fused_wide, MDE_WIDE_P=0), three runs bitwise."""
     import pymde_amd
     from pymde_amd.average_distortion import Binding, EdgePlan, fused_evaluate
     rng = np.random.default_rng(d)
@@ -1135,6 +1137,96 @@ def test_pipelined_wide_kernel_on_ragged_graphs(d, monkeypatch):
         outs[mode] = g
     # the two kernels add a row's half-edges in different groupings: equal to rounding, not bit for bit
     assert_grad_close(outs["1"], outs["0"])
+
+
+# ---------------------------------------------------------------- rows wider than the pipelined kernel takes (d > 512)
+_RAGGED_N = 257
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_graph():
+    """257 vertices, 1500 edges: every seventh row empty; vertex 3 a hub joined to every other non-empty vertex (220
+    half-edges: as long as a row of a simple graph gets here); 20 rows each of one, two and three half-edges; the
+    other rows share the remaining edges at random."""
+    rng = np.random.default_rng(257)
+    n, hub = _RAGGED_N, 3
+    others = rng.permutation([v for v in range(n) if v % 7 != 5 and v != hub])
+    ones, twos, threes, rest = others[:20], others[20:40], others[40:60], others[60:]
+    e = [(hub, v) for v in others]
+    e += [(v, rest[k]) for k, v in enumerate(twos)]
+    e += [(v, rest[2 * k + s]) for k, v in enumerate(threes) for s in (0, 1)]
+    pairs = np.stack(np.triu_indices(len(rest), 1), axis=1)
+    e += [(rest[a], rest[b]) for a, b in pairs[rng.choice(len(pairs), 1500 - len(e), replace=False)]]
+    e = np.array(e, dtype=np.int64)
+    e = np.unique(np.stack([e.min(1), e.max(1)], 1), axis=0)
+    deg = np.bincount(e.ravel(), minlength=n)
+    assert e.shape[0] == 1500 and deg[hub] == 220 and np.all(deg[np.arange(n) % 7 == 5] == 0)
+    assert np.all(deg[ones] == 1) and np.all(deg[twos] == 2) and np.all(deg[threes] == 3)
+    w = rng.uniform(0.5, 2.0, e.shape[0]).astype(np.float32)
+    return e, w
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_case(d):
+    """The ragged graph at dimension d: X, and loss and gradient of Log1p(1.5) in float64."""
+    e, w = _ragged_graph()
+    X = (np.random.default_rng(d).standard_normal((_RAGGED_N, d)) / np.sqrt(d)).astype(np.float32)
+    wE, wgrad = oracle.average_distortion(e, X, oracle.func("LOG1P", w, None, (1.5,)))
+    return X, wE, wgrad
+
+
+@pytest.mark.parametrize("d", [516, 1028, 515, 2047])
+def test_wide_rows_beyond_the_pipelined_kernel(d):
+    """k_fused_wide, the only fused kernel for d > 512: its 16-byte form <64, 4> and <64, 8> at d = 516 and 1028, its
+    4-byte form <64, 16> and <64, 32> at d = 515 and 2047 -- against the oracle, empty rows exactly zero, three runs
+    bitwise.  (An X that starts one float into its buffer would take the 4-byte form at d = 516, but fused_evaluate
+    copies such a view to an aligned tensor first: no such case here; test_unfused_paths_on_every_kernel has one.)"""
+    import pymde_amd
+    from pymde_amd.average_distortion import Binding, EdgePlan, fused_evaluate
+    n = _RAGGED_N
+    e, w = _ragged_graph()
+    X, wE, wgrad = _ragged_case(d)
+    b = Binding(EdgePlan(n, torch.tensor(e, device=DEV)), pymde_amd.penalties.Log1p(torch.tensor(w, device=DEV)))
+    Xt = torch.tensor(X, device=DEV)
+    runs = []
+    for _ in range(3):
+        buf = torch.zeros(n * d + 1, device=DEV)
+        fused_evaluate(b, Xt, buf[:n * d].view(n, d), buf[n * d:])
+        runs.append(buf)
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
+    g = runs[0][:n * d].view(n, d).cpu().numpy()
+    assert float(runs[0][n * d]) == pytest.approx(wE, rel=LOSS_RTOL)
+    assert_grad_close(g, wgrad)
+    assert np.all(g[np.arange(n) % 7 == 5] == 0.0)
+
+
+@pytest.mark.parametrize("path,d,offset", [("scatter", 3, 0), ("scatter", 8, 0), ("scatter", 516, 0),
+                                           ("distances", 516, 0), ("distances", 516, 1)])
+def test_unfused_paths_on_every_kernel(path, d, offset):
+    """mde_scatter and mde_distances_backward (parameters through the edge ids) through autograd on the ragged graph,
+    at the dimensions the tests above leave out: d = 3 the small-d kernels, d = 8 the pipelined kernel, d = 516
+    k_fused_wide -- its 4-byte form where X starts one float into its buffer.  Against float64."""
+    import pymde_amd
+    n = _RAGGED_N
+    e, w = _ragged_graph()
+    X, wE, wgrad = _ragged_case(d)
+    base = torch.zeros(n * d + offset, device=DEV)
+    base[offset:] = torch.tensor(X, device=DEV).reshape(-1)
+    Xt = base[offset:].view(n, d).requires_grad_(True)
+    assert Xt.data_ptr() % 16 == 4 * offset
+    if path == "scatter":
+        wt = torch.tensor(w, device=DEV)
+        mde = pymde_amd.MDE(n, d, e, lambda dist: wt * torch.log1p(dist.pow(1.5)))
+        assert not mde._binding().fused
+        E = mde.average_distortion(Xt)
+        E.backward()
+        assert float(E) == pytest.approx(wE, rel=1e-5)
+    else:
+        mde = pymde_amd.MDE(n, d, e, pymde_amd.penalties.Quadratic(torch.ones(len(e))))
+        gout = torch.linspace(0.5, 1.5, len(e), device=DEV)
+        (mde.distances(Xt) * gout).sum().backward()
+        wgrad = oracle.distances_backward(e, X, gout.cpu().numpy())
+    assert_grad_close(Xt.grad.cpu().numpy(), wgrad)
 
 
 @pytest.mark.parametrize("window,shuffle", [(60, True), (60, False), (0, True)])
