@@ -574,6 +574,21 @@ int mde_ann_search(int32_t nf, int32_t k, int32_t flags, int64_t n_q, const floa
  * centroids [n_lists, nf].  Checked on the host first (MDE_E_INVALID before any launch).  SYNC (the check). */
 int mde_ann_centroids(int64_t n, int32_t nf, const float* data, int64_t n_members, const int32_t* members,
                       int64_t n_lists, const int64_t* offsets, float* centroids, void* stream);
+/* One neighbour-of-neighbour pass over k-NN lists (csrc/mde_ann_refine.hip).  X [n, nf] are
+ * the prepared float32 rows and sqn their norms (mde_row_sqnorm).  idx_in int32 [n, k] / d2_in [n, k]: each
+ * row's valid entries ascending by (d2, index), -1 slots trailing, no self entry, no row twice.  rev int32
+ * [n, k]: reverse neighbours of every row (rows that list it), -1 padded.  Row i's candidates are rev[i] and
+ * the lists of every row of idx_in[i] and rev[i]; idx_out / d2_out (not the inputs: the pass reads the previous
+ * lists throughout) receive the k smallest of the old entries and the candidates under (d2, index), in the
+ * form of the inputs, empty slots as (-1, FLT_MAX).  A candidate's d2 is the float32 value the Euclidean
+ * searches give the pair, bit for bit, so an exact list is a fixed point.  changed_out: int32 on the device,
+ * the number of rows whose list changed.  work: mde_knn_refine_work_bytes(n, k) bytes; afterwards its first
+ * uint64 holds the number of distances the pass evaluated.  The output is the same on every run.
+ * 1 <= k <= 64, 1 <= n < 2^31; MDE_E_INVALID otherwise (the byte count: a negative MDE_E_* code). */
+int64_t mde_knn_refine_work_bytes(int64_t n, int32_t k);
+int mde_knn_refine(int64_t n, int32_t nf, const float* X, const float* sqn, int32_t k, const int32_t* idx_in,
+                   const float* d2_in, const int32_t* rev, int32_t* idx_out, float* d2_out, int32_t* changed_out,
+                   void* work, void* stream);
 /* Sparse data matrices (SURVEY 8f rows f2 / f4 on scipy.sparse inputs) [ref: preprocess/data_matrix.py:11-178].
  * Every entry below takes one device CSR of n rows and nf columns: indptr int64 [n + 1], indices int32
  * [nnz] (column ids, strictly increasing within a row), values float32 [nnz]; n < 2^31, nf < 2^31, nnz may

@@ -7,7 +7,10 @@ pynndescent above 10 000 items].
   2. every row is assigned to its nearest centroid and the rows are sorted by list (stable: id order
      within a list);
   3. each list probes the ``n_probe`` lists whose centroids are nearest to its own, itself first;
-  4. every query tile of 64 rows of a list is searched against the rows of its probed lists only.
+  4. every query tile of 64 rows of a list is searched against the rows of its probed lists only;
+  5. optionally (``n_refine``), neighbour-of-neighbour passes over the lists (``refine_lists``,
+     csrc/mde_ann_refine.hip): every row is offered its reverse neighbours and the lists of its forward and
+     reverse neighbours, which repairs the neighbours missed at the borders of the lists.
 
 The host side here is plumbing (sampling, sorting, offsets, the tile list); every distance is computed
 by the HIP kernels.  Recall depends on the data: it is high when the rows form clusters and poor on
@@ -184,15 +187,132 @@ def _sync(device):
     torch.cuda.synchronize(device)
 
 
-def knn_lists(X, k, n_lists=None, n_probe=None, seed=0, timings=None):
+def check_n_refine(n_refine):
+    """``n_refine`` as an int: the number of neighbour-of-neighbour passes.  A bool, a non-integer or a
+    negative value is a ``ValueError``.  Needs no device."""
+    if isinstance(n_refine, bool) or not isinstance(n_refine, int) or n_refine < 0:
+        raise ValueError(f"n_refine must be a non-negative integer, the number of refinement passes "
+                         f"(got {n_refine!r})")
+    return n_refine
+
+
+_D2_EMPTY = 0x7F7FFFFF   # the bits of FLT_MAX, the d2 of an empty slot
+_IDX_EMPTY = 0x7FFFFFFF
+
+
+def _list_keys(idx, d2):
+    """int64 [n, k] keys (bits of d2) << 32 | index whose order is (d2, index) for d2 >= 0; an entry that is
+    -1 gets the key of an empty slot, which follows every real one."""
+    empty = idx < 0
+    bits = d2.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    key = (bits << 32) | idx.long().clamp(min=0)
+    return torch.where(empty, torch.full_like(key, (_D2_EMPTY << 32) | _IDX_EMPTY), key)
+
+
+def _lists_of_keys(key):
+    """(idx int32 [n, k], d2 [n, k]) of sorted ``_list_keys``: empty slots are (-1, FLT_MAX)."""
+    low = key & 0xFFFFFFFF
+    idx = torch.where(low == _IDX_EMPTY, torch.full_like(low, -1), low).to(torch.int32)
+    d2 = (key >> 32).to(torch.int32).view(torch.float32)
+    return idx.contiguous(), d2.contiguous()
+
+
+def order_lists(X, idx):
+    """Valid neighbour lists (idx, d2) from arbitrary indices idx int32 [n, k] into the prepared float32 rows
+    X [n, nf]: each pair's float32 squared distance through ``mde_knn_ranks``' ``d2_out`` (the bits of the
+    searches), rows ordered by (d2, index), self entries, entries outside [0, n) and repeated rows dropped,
+    -1 slots trailing.  (The ranks that call also computes cost a pass over all pairs: this is for callers
+    that hand in their own lists, not for the lists of a search, which come with their distances.)"""
+    lib = _lib.load()
+    n, nf, k = int(X.shape[0]), int(X.shape[1]), int(idx.shape[1])
+    idx = idx.to(torch.int32).contiguous()
+    ranks = torch.empty((n, k), dtype=torch.int32, device=X.device)
+    d2 = torch.empty((n, k), dtype=torch.float32, device=X.device)
+    work = _lib.work_buffer(lib.mde_knn_ranks_work_bytes, n, n, k, 0, device=X.device)
+    _lib.check(lib.mde_knn_ranks(n, n, nf, _lib.ptr(X), _lib.ptr(X), 1, k, _lib.ptr(idx), 0, _lib.ptr(ranks),
+                                 _lib.ptr(d2), _lib.ptr(work), _lib.stream_ptr(X.device)))
+    rows = torch.arange(n, dtype=torch.int32, device=X.device)[:, None]
+    idx = torch.where((idx < 0) | (idx >= n) | (idx == rows), torch.full_like(idx, -1), idx)
+    key = torch.sort(_list_keys(idx, d2), 1).values
+    repeat = torch.zeros_like(key, dtype=torch.bool)
+    repeat[:, 1:] = key[:, 1:] == key[:, :-1]          # a row listed twice has one distance: adjacent keys
+    key = torch.sort(torch.where(repeat, torch.full_like(key, (_D2_EMPTY << 32) | _IDX_EMPTY), key), 1).values
+    return _lists_of_keys(key)
+
+
+def reverse_lists(idx, d2, cap=None):
+    """int32 [n, cap]: for every row t, among the rows j that list t (idx[j, s] == t), the ``cap`` (default
+    k) with the smallest (d2[j, s], j), in that order, -1 padded.  One stable sort of the n k entries by
+    (t, d2) -- they start in j order -- and offsets; d2 >= 0."""
+    n, k = int(idx.shape[0]), int(idx.shape[1])
+    cap = k if cap is None else int(cap)
+    device = idx.device
+    rev = torch.full((n, cap), -1, dtype=torch.int32, device=device)
+    target = idx.reshape(-1).long()
+    listed = target >= 0
+    bits = d2.contiguous().view(torch.int32).reshape(-1).long() & 0xFFFFFFFF
+    source = torch.arange(n, dtype=torch.int64, device=device).repeat_interleave(k)[listed]
+    key = ((target << 32) | bits)[listed]
+    key, order = torch.sort(key, stable=True)
+    target = key >> 32
+    first = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    first[1:] = torch.cumsum(torch.bincount(target, minlength=n), 0)
+    place = torch.arange(key.shape[0], dtype=torch.int64, device=device) - first[target]
+    keep = place < cap
+    rev[target[keep], place[keep]] = source[order][keep].to(torch.int32)
+    return rev
+
+
+def refine_lists(X, idx, d2=None, n_iters=1, sqn=None, evaluated=None):
+    """``n_iters`` neighbour-of-neighbour passes (``mde_knn_refine``, csrc/mde_ann_refine.hip) over the
+    neighbour lists idx int32 [n, k] / d2 [n, k] of the prepared float32 rows X [n, nf], at any n.
+
+    Each row's valid entries ascend by (d2, index), -1 slots trail, no row lists itself or another twice;
+    with ``d2=None`` the lists are first put into that form by ``order_lists``.  A pass offers every row its
+    reverse neighbours (``reverse_lists``) and the lists of its forward and reverse neighbours, and keeps the
+    k smallest under (d2, index): entries only move earlier, every distance is the float32 value of the
+    searches, an exact list stays as it is.  Returns (idx, d2, changed): ``changed`` is the list of
+    per-pass counts of rows whose list changed; the passes stop early after one that changes none.
+    ``evaluated``, when a list, receives the number of distances each pass computed."""
+    lib = _lib.load()
+    n, nf, k = int(X.shape[0]), int(X.shape[1]), int(idx.shape[1])
+    device = X.device
+    if d2 is None:
+        idx, d2 = order_lists(X, idx)
+    idx, d2 = idx.to(torch.int32).contiguous(), d2.to(torch.float32).contiguous()
+    if sqn is None:
+        sqn = _row_sqnorm(X)
+    changed = []
+    work = _lib.work_buffer(lib.mde_knn_refine_work_bytes, n, k, device=device)
+    count = torch.zeros(1, dtype=torch.int32, device=device)
+    for _ in range(check_n_refine(n_iters)):
+        rev = reverse_lists(idx, d2)
+        idx_new, d2_new = torch.empty_like(idx), torch.empty_like(d2)
+        _lib.check(lib.mde_knn_refine(n, nf, _lib.ptr(X), _lib.ptr(sqn), k, _lib.ptr(idx), _lib.ptr(d2),
+                                      _lib.ptr(rev), _lib.ptr(idx_new), _lib.ptr(d2_new), _lib.ptr(count),
+                                      _lib.ptr(work), _lib.stream_ptr(device)))
+        idx, d2 = idx_new, d2_new
+        changed.append(int(count.item()))
+        if evaluated is not None:
+            evaluated.append(int(work[:8].view(torch.int64).item()))
+        if changed[-1] == 0:
+            break
+    return idx, d2, changed
+
+
+def knn_lists(X, k, n_lists=None, n_probe=None, seed=0, timings=None, n_refine=0):
     """Approximate directed neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the
-    GPU, in the caller's row order.  Rows with fewer than k candidates get -1 slots.
+    GPU, in the caller's row order.  Rows with fewer than k candidates get -1 slots.  ``n_refine`` passes of
+    ``refine_lists`` follow the scan (0: none, and nothing else is launched).
 
     ``timings``, when a dict, receives the seconds of each stage (synchronising between them) and the
-    sizes of the lists, the tile count and the load imbalance of the scan."""
+    sizes of the lists, the tile count and the load imbalance of the scan; with ``n_refine`` also the
+    ``"refine"`` lap, the rows each pass changed (``"refine_changed"``) and the distances it evaluated
+    (``"refine_evaluated"``)."""
     n, nf = int(X.shape[0]), int(X.shape[1])
     device = X.device
     n_lists, n_probe = resolve_params(n, n_lists, n_probe)
+    n_refine = check_n_refine(n_refine)
     timed = timings is not None
     clock = _Clock(device, timed)
     sqn = _row_sqnorm(X)
@@ -209,6 +329,12 @@ def knn_lists(X, k, n_lists=None, n_probe=None, seed=0, timings=None):
     clock.lap(timings, "probe")
     idx, d2 = search(X, sqn, X, sqn, k, offsets, probe, tiles, q_map=perm, b_map=perm, flags=SELF | SCATTER)
     clock.lap(timings, "scan")
+    if n_refine:
+        evaluated = [] if timed else None
+        idx, d2, changed = refine_lists(X, idx, d2, n_iters=n_refine, sqn=sqn, evaluated=evaluated)
+        clock.lap(timings, "refine")
+        if timed:
+            timings.update(refine_changed=changed, refine_evaluated=evaluated)
     if timed:
         sizes = offsets_h[1:] - offsets_h[:-1]
         timings.update(n_lists=n_lists, n_probe=n_probe, list_sizes=sizes, tiles=int(tiles_h.shape[0]),

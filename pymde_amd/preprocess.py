@@ -162,7 +162,7 @@ def _neighbor_lists_to_graph(n, k, idx, values, max_value, device):
 
 def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,
                         n_lists=None, n_probe=None, seed=0, verbose=False, metric="euclidean",
-                        precision="float32", n_candidates=None):
+                        precision="float32", n_candidates=None, n_refine=0):
     """Exact k-nearest-neighbour graph of the rows of a data matrix (Euclidean distance by default)
     [ref: preprocess/data_matrix.py:91-178] or of the nodes of a ``Graph`` (shortest-path metric,
     ``pymde_amd.graph.k_nearest_neighbors``) [ref: preprocess/generic.py dispatch].
@@ -193,6 +193,15 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     ``verbose=True`` the sizes of the lists and a recall@k estimated from 1 000 sampled rows against the
     exact search are logged.  Sparse inputs are densified (an error if the dense copy does not fit);
     ``Graph`` inputs have no approximate search.
+
+    ``n_refine`` (with ``approximate=True``; default 0) runs that many neighbour-of-neighbour passes over the
+    lists of the inverted file (``ann.refine_lists``, ``csrc/mde_ann_refine.hip``): every row is offered the
+    rows that list it and the lists of its forward and reverse neighbours, and keeps the k nearest.  A pass
+    repairs the neighbours missed at the borders of the lists at a few hundred distances per row; it only
+    ever replaces an entry by a nearer one, and it does not rescue a search that probes far too few lists.
+    Every metric and input form of the approximate search takes it, ``max_distance`` applies afterwards and
+    the logged recall is that of the refined lists.  With ``approximate=False`` it is a ``ValueError`` (an
+    exact list is a fixed point of the pass); below 10 000 rows it is not used, like ``n_probe``.
 
     ``data`` is a dense ``np.ndarray`` / ``torch.Tensor`` [n, n_features], a sparse data matrix (a
     scipy sparse matrix of any format, or a torch sparse COO / CSR tensor; searched by the sparse
@@ -227,6 +236,10 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     metric = _metrics.resolve(metric)
     _metrics.check_approximate(metric, approximate)
     precision = _check_precision_arguments(precision, n_candidates, k, metric, approximate, _is_graph(data))
+    n_refine = _ann.check_n_refine(n_refine)
+    if n_refine and not approximate:
+        raise ValueError("n_refine refines the lists of approximate=True; the exact search has nothing to refine "
+                         "(an exact list is a fixed point of the pass)")
     if hasattr(data, "edges") and hasattr(data, "n_items") and not isinstance(data, torch.Tensor):
         _metrics.check_graph(metric)
         if approximate:
@@ -236,7 +249,7 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
                                           max_distance=max_distance)
     if metric != _metrics.EUCLIDEAN:
         idx, values, bound = _metric_knn_lists(data, k, metric, max_distance, device, approximate, n_lists,
-                                               n_probe, seed, verbose, precision, n_candidates)
+                                               n_probe, seed, verbose, precision, n_candidates, n_refine)
         return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
     if _sparse.is_sparse(data):
         csr = _sparse.to_device_csr(data, device)
@@ -249,7 +262,8 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
                     f"approximate=True densifies sparse data, and the dense copy of this {csr.n} x "
                     f"{csr.n_features} matrix does not fit in the device memory allowed for it; "
                     "use approximate=False (the exact sparse kernel)")
-            idx, d2 = _euclidean_knn_lists(csr.to_dense(), k, True, n_lists, n_probe, seed, verbose)
+            idx, d2 = _euclidean_knn_lists(csr.to_dense(), k, True, n_lists, n_probe, seed, verbose,
+                                           n_refine=n_refine)
         elif _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
             idx, d2 = _euclidean_knn_lists(csr.to_dense(), k, verbose=verbose, precision=precision,
                                            n_candidates=n_candidates)
@@ -270,7 +284,8 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     k = _clamp_k(k, n)
     if approximate:
         _ann.resolve_params(n, n_lists, n_probe)      # the same argument checks at every size
-    idx, d2 = _euclidean_knn_lists(data, k, approximate, n_lists, n_probe, seed, verbose, precision, n_candidates)
+    idx, d2 = _euclidean_knn_lists(data, k, approximate, n_lists, n_probe, seed, verbose, precision, n_candidates,
+                                   n_refine)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
     return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
 
@@ -281,7 +296,7 @@ _BF16_SPARSE_DOES_NOT_FIT = (
 
 
 def _metric_knn_lists(data, k, metric, max_distance=None, device=None, approximate=False, n_lists=None,
-                      n_probe=None, seed=0, verbose=False, precision=FLOAT32, n_candidates=None):
+                      n_probe=None, seed=0, verbose=False, precision=FLOAT32, n_candidates=None, n_refine=0):
     """Directed neighbour lists of a data matrix under cosine, correlation or Manhattan (a canonical name):
     ``(idx [n, k] int32, values [n, k], bound)``.  ``values`` are what the kernels rank by -- the squared
     chord ``d2 = 2 (1 - cos)`` of the unit rows for cosine / correlation, the distance itself for Manhattan
@@ -325,7 +340,7 @@ def _metric_knn_lists(data, k, metric, max_distance=None, device=None, approxima
             raise ValueError(_BF16_SPARSE_DOES_NOT_FIT.format(n=csr.n, nf=csr.n_features))
         idx, values = _sparse_knn_lists(csr, k)
     elif approximate and n >= _ann.MIN_ITEMS:
-        idx, values = _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
+        idx, values = _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose, n_refine)
     elif precision == BFLOAT16:
         # the unit rows are searched as they are by the float32 kernel; the bfloat16 copy is centred
         idx, values = _bf16_self_search(data, k, n_candidates, _bf16_mu(data), verbose, seed)
@@ -346,7 +361,7 @@ def _clamp_k(k, n):
 
 
 def _euclidean_knn_lists(data, k, approximate=False, n_lists=None, n_probe=None, seed=0, verbose=False,
-                         precision=FLOAT32, n_candidates=None):
+                         precision=FLOAT32, n_candidates=None, n_refine=0):
     """Directed Euclidean neighbour lists (idx [n, k] int32, d2 [n, k]) of a dense float32 [n, nf] on the GPU:
     what ``k_nearest_neighbors`` calls for Euclidean data.  The search -- exact, or the inverted file with its
     recall estimate when ``approximate`` and n >= ``ann.MIN_ITEMS`` -- runs on the rows minus their float64
@@ -359,7 +374,7 @@ def _euclidean_knn_lists(data, k, approximate=False, n_lists=None, n_probe=None,
         return _bf16_self_search(rows, k, n_candidates, mu, verbose, seed)
     data, _ = _metrics.translated_rows(data)
     if approximate and int(data.shape[0]) >= _ann.MIN_ITEMS:
-        return _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose)
+        return _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose, n_refine)
     return _dense_knn_lists(data, k)
 
 
@@ -589,14 +604,16 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
     return idx, dist
 
 
-def _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose):
-    """Directed neighbour lists of a dense float32 [n, nf] on the GPU by the inverted-file search."""
+def _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose, n_refine=0):
+    """Directed neighbour lists of a dense float32 [n, nf] on the GPU by the inverted-file search and
+    ``n_refine`` neighbour-of-neighbour passes over its lists."""
     n_lists, n_probe = _ann.resolve_params(int(data.shape[0]), n_lists, n_probe)
     if k > _ann.MAX_K:      # the exact kernel's error, before any work
         raise _lib.MdeHipError(_lib.MDE_E_INVALID, "mde_ann_search: invalid arguments (1 <= k <= %d)" % _ann.MAX_K)
     stats = {} if verbose else None
     with torch.cuda.device(data.device):
-        idx, d2 = _ann.knn_lists(data, k, n_lists=n_lists, n_probe=n_probe, seed=seed, timings=stats)
+        idx, d2 = _ann.knn_lists(data, k, n_lists=n_lists, n_probe=n_probe, seed=seed, timings=stats,
+                                 n_refine=n_refine)
     if verbose:
         sizes = stats["list_sizes"].double()
         _LOGGER.info(
@@ -604,6 +621,9 @@ def _approximate_knn_lists(data, k, n_lists, n_probe, seed, verbose):
             f"{int(sizes.median())}, max {int(sizes.max())}), {n_probe} probed per list, "
             f"{stats['candidate_pairs'] / float(data.shape[0]) ** 2:.3f} of all pairs scanned in "
             f"{stats['tiles']} tiles (estimated load imbalance {stats['imbalance']:.2f})")
+        if n_refine:
+            _LOGGER.info(f"approximate {k}-NN: {len(stats['refine_changed'])} refinement pass(es) changed "
+                         f"{stats['refine_changed']} rows")
         recall = _estimated_recall(data, idx, k, seed=seed)
         _LOGGER.info(f"approximate {k}-NN: estimated recall@{k} {recall:.3f} (1000 sampled rows)")
     return idx, d2

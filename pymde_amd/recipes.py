@@ -243,7 +243,8 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
 
     ``approximate_neighbors`` (data matrices only): ``True`` builds the k-NN graph by the approximate
     inverted-file search of ``preprocess.k_nearest_neighbors(approximate=True)`` with its defaults, a dict
-    ``{"n_lists": .., "n_probe": ..}`` sets those knobs; ``False`` (the default) keeps the exact search.
+    ``{"n_lists": .., "n_probe": .., "n_refine": ..}`` sets those knobs (``n_refine``: neighbour-of-neighbour
+    passes over the lists, default 0); ``False`` (the default) keeps the exact search.
     Recall depends on the data; ``verbose=True`` logs an estimate.
 
     ``metric`` (data matrices only): the distance in the original data under which neighbours are taken,
@@ -476,16 +477,16 @@ def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repu
 def _approximate_options(approximate_neighbors):
     """Keywords of ``preprocess.k_nearest_neighbors`` for a recipe's ``approximate_neighbors`` value:
     False -> {} (the exact search), True -> approximate with the defaults, a dict -> approximate with
-    its ``n_lists`` / ``n_probe``."""
+    its ``n_lists`` / ``n_probe`` / ``n_refine``."""
     if approximate_neighbors is None or approximate_neighbors is False:
         return {}
     if approximate_neighbors is True:
         return {"approximate": True}
     if isinstance(approximate_neighbors, dict):
-        unknown = set(approximate_neighbors) - {"n_lists", "n_probe"}
+        unknown = set(approximate_neighbors) - {"n_lists", "n_probe", "n_refine"}
         if unknown:
             raise ValueError(f"approximate_neighbors: unknown keys {sorted(unknown)}; "
-                             "the knobs are 'n_lists' and 'n_probe'")
+                             "the knobs are 'n_lists', 'n_probe' and 'n_refine'")
         return dict(approximate_neighbors, approximate=True)
     raise ValueError("approximate_neighbors must be True, False or a dict {'n_lists': .., 'n_probe': ..}")
 
