@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 
 #include "../../include/mde_hip.h"
@@ -15,6 +16,8 @@
 // row-sharded solve sums the ranks' shares before the one rounding to float, mde_plan_loss_double)
 #define MDE_PARTIALS_LOSS_D (MDE_MAX_PARTIALS + 2)
 #define MDE_PARTIALS_DOUBLES (MDE_MAX_PARTIALS + 4)
+
+#define MDE_INTERNAL __attribute__((visibility("hidden")))  // crosses translation units, not the library's boundary
 
 void mde_set_error(const char* fmt, ...);
 int mde_hip_fail(hipError_t e, const char* what, const char* file, int line);
@@ -40,6 +43,49 @@ static inline int mde_grid(int64_t items, int per_block, int max_blocks = 2048) 
   if (b > max_blocks) b = max_blocks;
   return (int)b;
 }
+
+// tuning / test switches: read per call, so that a test can change one inside a process
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// Owner of one hipMalloc allocation (host code, move-only): freed when the owner goes out of scope, unless
+// release() has handed the pointer to somebody who keeps it.
+template <typename T>
+class MdeDeviceBuf {
+ public:
+  MdeDeviceBuf() = default;
+  MdeDeviceBuf(MdeDeviceBuf&& o) noexcept : p_(o.release()) {}
+  MdeDeviceBuf& operator=(MdeDeviceBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.release();
+    }
+    return *this;
+  }
+  ~MdeDeviceBuf() { reset(); }
+  hipError_t alloc(size_t bytes) {
+    reset();
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), bytes);
+    if (e != hipSuccess) p_ = nullptr;
+    return e;
+  }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  T* release() {
+    T* p = p_;
+    p_ = nullptr;
+    return p;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
 
 // ---------------------------------------------------------------- device helpers
 #if defined(__HIPCC__)

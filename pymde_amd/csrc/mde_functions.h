@@ -329,11 +329,19 @@ struct MdeFuncArgs {
   int kind, kind_neg;
   MdeScalars S, N;
 };
+static inline MdeFuncArgs func_args(const mde_func* f) {
+  MdeFuncArgs a;
+  a.kind = f->kind;
+  a.kind_neg = f->kind_neg;
+  a.S = {f->s0, f->s1, f->s2};
+  a.N = {f->n0, f->n1, f->n2};
+  return a;
+}
 
 // universal: every kind, PushAndPull by sign of the weight (penalties.py:390: w >= 0 attractive)
 // kFiniteG: f'/d is finite for every finite parameter and distance (no NaN/Inf fix-up needed when
 // the caller knows the parameters are finite)
-// kRingFused: the LDS-ring kernel spells the evaluation out itself (mde_ring.hip: Log1p with exponent
+// kRingFused: the LDS-ring kernel spells the evaluation out itself (mde_ring_kernel.h: Log1p with exponent
 // 1.5, parameters pre-multiplied by kParamScale) instead of calling eval()
 struct FnRuntime {
   static constexpr bool kFiniteG = false;

@@ -2,13 +2,9 @@
 // stores for d <= 4, the functors of the two unfused paths, the launch arguments
 // and the entry points of the units (mde_distortion.hip picks one of them per call).
 #pragma once
-#include <stdlib.h>
-
 #include "mde_common.h"
 #include "mde_functions.h"
 #include "mde_plan.h"
-
-#define MDE_INTERNAL __attribute__((visibility("hidden")))
 
 // ---------------------------------------------------------------- device pieces
 // The parameters (a0, a1) of half-edge position h: one value for every edge (scalar), one per
@@ -121,20 +117,6 @@ static inline int fused_row_grid(FusedArgs& A, int lanes) {
   return nrows;
 }
 
-// tuning / test switches: read per call, so that a test can change one inside a process
-static inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-static inline MdeFuncArgs func_args(const mde_func* f) {
-  MdeFuncArgs a;
-  a.kind = f->kind;
-  a.kind_neg = f->kind_neg;
-  a.S = {f->s0, f->s1, f->s2};
-  a.N = {f->n0, f->n1, f->n2};
-  return a;
-}
 // the one compile-time functor of the general-d kernels: Log1p(1.5), the recipes' default attractive
 // penalty (config 5, d = 128: the run-time functor's switch and general pow cost 0.5 ms of the 3.7 ms
 // launch)

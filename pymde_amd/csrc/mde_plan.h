@@ -2,7 +2,8 @@
 #pragma once
 #include "mde_common.h"
 
-// LDS-ring layout of the small-d kernel (mde_ring.hip; built lazily, per embedding dim).
+// LDS-ring layout of the small-d kernel (decided in mde_ring.hip, built by mde_ring_build.hip; lazily, per
+// embedding dim).
 // A workgroup (row block rb, column group qg) runs MDE_RING_NCW consumer waves; the
 // stream of consumer wave w is the wave iterations [wave_iter[s], wave_iter[s + 1]) with
 // s = (rb * col_groups + qg) * NCW + w, 64 packed half-edges each, chunk-major.
@@ -16,20 +17,20 @@ struct mde_ring_layout {
   int ring_off = 0, slots = 0;  // LDS byte offset of the chunk ring and its number of slots (depend on rows_per_block)
   int64_t n_iters = 0;          // wave iterations of all streams
   int64_t H = 0;                // padded entry count = 64 * n_iters
-  uint32_t* packed = nullptr;   // [H] absolute LDS addresses of x_v and x_u (ring_pack_word, mde_ring.hip)
+  uint32_t* packed = nullptr;   // [H] absolute LDS addresses of x_v and x_u (ring_pack_word, mde_ring.h)
   int32_t* eid = nullptr;       // [H] original edge id (parameter expansion), -1 for padding
   uint32_t* hdr = nullptr;      // [2 * n_iters] chunk window | padding flag and loss class of an iteration
   int32_t* wave_iter = nullptr; // [n_row_blocks * col_groups * NCW + 1]
   float* partial = nullptr;     // [Q * nloc * d] per-group gradient partials (Q > 1 only)
-  // Round 6 -- graphs the equal-rows, everybody-in-the-ring layout gave up on (mde_ring.hip, plan_rows):
+  // Round 6 -- graphs the equal-rows, everybody-in-the-ring layout gave up on (mde_ring_rows.h, plan_rows):
   //  * PERMUTED row blocks: slot_row[rb * rows_per_block + s] = local row whose x_v / accumulator live in LDS slot s
   //    of row block rb (-1: unused), rows dealt to the blocks so that every block holds the same number of
   //    half-edges whatever the degrees do along the vertex order; nullptr: slot s of block rb is row rb * R + s.
   //    A permuted layout adds EVERY entry's loss term with weight 1/2 (the rows of a wave are no longer a range of
   //    the vertex order, so "the entry whose row is the smaller vertex" would be a per-lane test everywhere).
   //  * PEELED hub rows: rows with more half-edges than a wave's stream can take one per iteration are left out of
-  //    the ring streams; k_hub_rows / k_hub_finish (mde_ring.hip) evaluate them from the CSR plan in segments of
-  //    MDE_HUB_SEG positions, behind the ring kernel on the same stream (one writer per row, fixed order).
+  //    the ring streams; k_hub_rows / k_hub_finish (mde_ring_hub.hip) evaluate them from the CSR plan in segments of
+  //    MDE_HUB_SEG positions (mde_ring_rows.h), behind the ring kernel on the same stream (one writer per row, fixed order).
   int32_t* slot_row = nullptr;
   int count_all = 0;            // 1: every entry adds f / 2 (permuted layouts); 0: the smaller endpoint adds f
   int loss_band = 0;            // W of ring_counts (mde_ring.h), in vertices; 0: the smaller endpoint adds f
@@ -42,7 +43,6 @@ struct mde_ring_layout {
   int32_t* hub_first = nullptr; // [n_hub_rows + 1] first segment of each hub row
   double* hub_partial = nullptr;  // [n_hub_segs][8]: sum g (x_v - x_u) [<= 4] | loss
 };
-#define MDE_HUB_SEG 512
 
 struct mde_plan {
   int64_t n = 0, p = 0, H = 0, row_lo = 0, row_hi = 0;

@@ -1,6 +1,7 @@
-// mde_ring.h -- geometry of the LDS-ring kernel (layout 1), shared by the layout builder and the
-// dispatcher (mde_ring.hip), the kernel template (mde_ring_kernel.h) and the translation units that
-// instantiate it (mde_ring_k_*.hip).
+// mde_ring.h -- geometry of the LDS-ring kernel (layout 1), shared by the layout decision and the
+// dispatcher (mde_ring.hip), the layout builder (mde_ring_build.hip), the parameter streams, self-checks and
+// hub rows (mde_ring_params / _check / _hub.hip), the kernel template (mde_ring_kernel.h) and the
+// translation units that instantiate it (mde_ring_k_*.hip).
 #pragma once
 #include "mde_common.h"
 #include "mde_functions.h"
@@ -143,15 +144,6 @@ struct RingArgs {
   double loss_scale;
 };
 
-inline MdeFuncArgs ring_func_args(const mde_func* f) {
-  MdeFuncArgs a;
-  a.kind = f->kind;
-  a.kind_neg = f->kind_neg;
-  a.S = {f->s0, f->s1, f->s2};
-  a.N = {f->n0, f->n1, f->n2};
-  return a;
-}
-
 // The instantiations of k_fused_ring live in one translation unit per family of distortion functions:
 // HIP loads a unit's code object on the first launch of one of its kernels, and a process uses one
 // family -- with everything in one unit the first launch paid ~22 ms for 15 MB of code it never ran
@@ -165,3 +157,5 @@ int mde_ring_launch_loss(const RingArgs& A, const mde_func* f, int* nblocks);   
 int mde_ring_launch_penalty2(const RingArgs& A, const mde_func* f, int* nblocks);  // mde_ring_k_penalty2.hip
 int mde_ring_launch_loss2(const RingArgs& A, const mde_func* f, int* nblocks);     // mde_ring_k_loss2.hip
 int mde_ring_launch_runtime(const RingArgs& A, const mde_func* f, int* nblocks);   // mde_ring_k_runtime.hip
+// ... and the peeled hub rows behind any of them, on the same stream (MDE_OK or an error)
+int mde_ring_launch_hub(const RingArgs& A, const mde_func* f);                     // mde_ring_hub.hip

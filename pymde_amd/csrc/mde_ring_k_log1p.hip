@@ -4,7 +4,7 @@
 
 int mde_ring_launch_log1p(const RingArgs& A, const mde_func* f, int* nblocks) {
   if ((A.d != 2 && A.d != 3) || f->kind_neg != MDE_F_NONE || f->kind != MDE_F_LOG1P) return 0;
-  const MdeFuncArgs a = ring_func_args(f);
+  const MdeFuncArgs a = func_args(f);
   // LIN: a padding lane's parameter 0 gives f = 0 whatever its distance is
   switch (mde_exp_class(f->s0)) {
     case 2: MDE_RING23(FnSingle<MDE_F_LOG1P COMMA 2>, true);

@@ -9,7 +9,7 @@ int mde_ring_launch_loss(const RingArgs& A, const mde_func* f, int* nblocks) {
   return 0;
 #else
   if ((A.d != 2 && A.d != 3) || f->kind_neg != MDE_F_NONE) return 0;
-  const MdeFuncArgs a = ring_func_args(f);
+  const MdeFuncArgs a = func_args(f);
   switch (f->kind) {
     case MDE_F_L_QUADRATIC: MDE_RING23(FnSingle<MDE_F_L_QUADRATIC COMMA 0>, false);
     case MDE_F_L_WEIGHTED_QUADRATIC: MDE_RING23(FnSingle<MDE_F_L_WEIGHTED_QUADRATIC COMMA 0>, false);

@@ -8,7 +8,7 @@ int mde_ring_launch_loss2(const RingArgs& A, const mde_func* f, int* nblocks) {
   return 0;
 #else
   if ((A.d != 2 && A.d != 3) || f->kind_neg != MDE_F_NONE) return 0;
-  const MdeFuncArgs a = ring_func_args(f);
+  const MdeFuncArgs a = func_args(f);
   switch (f->kind) {
     case MDE_F_L_CUBIC: MDE_RING23(FnSingle<MDE_F_L_CUBIC COMMA 0>, false);
     case MDE_F_L_POWER: MDE_RING23(FnSingle<MDE_F_L_POWER COMMA 0>, false);

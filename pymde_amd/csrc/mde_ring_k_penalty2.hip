@@ -9,7 +9,7 @@ int mde_ring_launch_penalty2(const RingArgs& A, const mde_func* f, int* nblocks)
   return 0;
 #else
   if ((A.d != 2 && A.d != 3) || f->kind_neg != MDE_F_NONE) return 0;
-  const MdeFuncArgs a = ring_func_args(f);
+  const MdeFuncArgs a = func_args(f);
   const int ea = mde_exp_class(f->s0);
   switch (f->kind) {
     // w = 0 gives f = 0 whatever the distance (softplus, sigmoid and the hinge are finite): LIN

@@ -6,7 +6,7 @@ int mde_ring_launch_runtime(const RingArgs& A, const mde_func* f, int* nblocks) 
 #ifdef MDE_RING_MINIMAL
   return 0;
 #else
-  FnRuntime fn{ring_func_args(f)};
+  FnRuntime fn{func_args(f)};
   int rc;
   switch (A.d) {
     case 1: rc = launch_ring<1, FnRuntime, false>(A, fn, nblocks); break;
