@@ -125,7 +125,9 @@ typedef struct mde_func {
   const float* a1;   /* device; second per-edge array (weighted losses) or NULL           */
   int32_t a0_scalar; /* 1: a0 points at ONE value broadcast to every edge (nelement()==1);
                         2: a0 is a codebook stream written by mde_plan_expand_codebook (layout 1);
-                        3: a0 is a byte-index stream written by mde_plan_expand_bytes (layout 1)  */
+                        3: a0 is a byte-index stream written by mde_plan_expand_bytes (layout 1);
+                        4: a0 is a PAIR codebook stream written by mde_plan_expand_codebook_for (layout 1):
+                           one or two distinct values, selected by bit 0 of the packed word             */
   int32_t a1_scalar;
   float s0, s1, s2;  /* scalars of `kind`                                                 */
   float n0, n1, n2;  /* scalars of `kind_neg`                                             */
@@ -204,6 +206,19 @@ int64_t mde_plan_layout_half_edges(const mde_plan* plan, int32_t layout);
  * fix-up of f'/d for codebook streams).  Results are identical either way.  SYNC. */
 int mde_plan_expand_codebook(const mde_plan* plan, const float* in_edge, float* out_half,
                              int32_t* n_values_host, void* stream);
+/* The same for the function the stream is meant for, which allows a second form.  *form_host receives the value
+ * for mde_func.a0_scalar (0 with *n_values_host = 0):
+ *   2  the codebook above;
+ *   4  the pair codebook, taken when `in_edge` holds ONE or TWO distinct values (unit weights, the {1, 2} of a
+ *      neighbour graph) and `f` is a function whose entries with coinciding ends add exactly zero for every finite
+ *      parameter (Log1p with exponent 1, 1.5 or 2).  The value table starts with the two values (one value: twice),
+ *      the index is bit 0 of the packed word, and the kernel selects between two registers instead of reading the
+ *      table from LDS.  Padding entries select entry 0, a real weight: their column field is rewritten to their own
+ *      (dummy, zero) row, so their distance is 0.  The stream fits `f` only (kind, kind_neg and s0 are read;
+ *      a0 need not be set yet).  MDE_CODEBOOK_PAIR=0 in the environment: always form 2.
+ * Results are bitwise identical between the two forms.  SYNC. */
+int mde_plan_expand_codebook_for(const mde_plan* plan, const mde_func* f, const float* in_edge, float* out_half,
+                                 int32_t* n_values_host, int32_t* form_host, void* stream);
 /* Byte-index parameter stream for layout 1 at d = 2 and d = 3: when `in_edge` [p] holds at most 255 distinct
  * values (the hop-count deviations of preserve_distances on a graph [ref: pymde/recipes.py:194-215,
  * preprocess/graph.py:402-474], quantised weights) write to out_half [mde_plan_layout_half_edges(plan, 1)

@@ -72,6 +72,8 @@ SYMBOLS = {
     "mde_lbfgs_dev_dots": (c_i32, [c_vp]),
     "mde_rank_reduce": (c_i32, [c_i32, c_i32, ctypes.c_uint64, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mde_plan_expand_codebook": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), c_vp]),
+    "mde_plan_expand_codebook_for": (c_i32, [c_vp, ctypes.POINTER(MdeFunc), c_vp, c_vp, ctypes.POINTER(c_i32),
+                                             ctypes.POINTER(c_i32), c_vp]),
     "mde_plan_expand_bytes": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), c_vp]),
     "mde_plan_expand_layout": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mde_edges_deduplicate": (c_i32, [c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),

@@ -88,20 +88,28 @@ class EdgePlan(object):
                                                   _lib.ptr(out), _lib.stream_ptr(self.device)))
         return out
 
-    def expand_codebook(self, per_edge):
+    def expand_codebook(self, per_edge, spec=None):
         """Layout 1 only: the codebook form of a per-edge array with at most 7 distinct values
-        (``mde_plan_expand_codebook``), or None when it does not apply."""
+        (``mde_plan_expand_codebook``), or None when it does not apply.  With the function's ``spec``
+        (``mde_plan_expand_codebook_for``) the result is ``(stream or None, a0_scalar code)``: 2, or 4 for the pair
+        codebook of one or two values under a function that allows it."""
         lib = _lib.load()
         t = per_edge.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
         if t.numel() != self.p:
-            return None
+            return None if spec is None else (None, 0)
         size = int(lib.mde_plan_layout_half_edges(self._handle, 1))
         out = torch.empty(max(size, 1), dtype=torch.float32, device=self.device)
-        nv = ctypes.c_int32(0)
+        nv, form = ctypes.c_int32(0), ctypes.c_int32(0)
         with torch.cuda.device(self.device):
-            _lib.check(lib.mde_plan_expand_codebook(self._handle, _lib.ptr(t), _lib.ptr(out),
-                                                    ctypes.byref(nv), _lib.stream_ptr(self.device)))
-        return out if nv.value > 0 else None
+            if spec is None:
+                _lib.check(lib.mde_plan_expand_codebook(self._handle, _lib.ptr(t), _lib.ptr(out),
+                                                        ctypes.byref(nv), _lib.stream_ptr(self.device)))
+                return out if nv.value > 0 else None
+            f = spec.to_struct(out, None)   # (kind, kind_neg and the scalars are what is read)
+            _lib.check(lib.mde_plan_expand_codebook_for(self._handle, ctypes.byref(f), _lib.ptr(t), _lib.ptr(out),
+                                                        ctypes.byref(nv), ctypes.byref(form),
+                                                        _lib.stream_ptr(self.device)))
+        return (out, form.value) if nv.value > 0 else (None, 0)
 
     def expand_bytes(self, per_edge):
         """Layout 1 only: the byte-index form of a per-edge array with at most 255 distinct values
@@ -228,9 +236,10 @@ class Binding(object):
                     return a.detach().to(device=plan.device, dtype=torch.float32).reshape(1).contiguous()
                 return plan.expand(a, layout)
             # few distinct first parameters (k-NN weights): 4-byte codebook stream instead of 8 bytes
-            a0 = None
+            # (one or two values under a function whose coinciding entries add zero: the pair codebook, a0_scalar 4)
+            a0, codebook_form = None, 0
             if layout == 1 and spec.a0 is not None and spec.a0.numel() > 1:
-                a0 = plan.expand_codebook(spec.a0)
+                a0, codebook_form = plan.expand_codebook(spec.a0, spec)
             self.codebook = a0 is not None
             # ... up to 255: one index byte per entry beside the packed words, 5 bytes (hop-count deviations)
             self.byte_stream = False
@@ -252,7 +261,7 @@ class Binding(object):
             self._struct.e0 = e0.data_ptr() if e0 is not None else None
             self._struct.e1 = e1.data_ptr() if e1 is not None else None
             if self.codebook:
-                self._struct.a0_scalar = 2
+                self._struct.a0_scalar = codebook_form
             elif self.byte_stream:
                 self._struct.a0_scalar = 3
             self.stream_kind = ("codebook" if self.codebook else "byte index" if self.byte_stream else

@@ -343,8 +343,19 @@ static inline MdeFuncArgs func_args(const mde_func* f) {
 // the caller knows the parameters are finite)
 // kRingFused: the LDS-ring kernel spells the evaluation out itself (mde_ring_kernel.h: Log1p with exponent
 // 1.5, parameters pre-multiplied by kParamScale) instead of calling eval()
+// kZeroAtZero: an entry whose two ends coincide adds nothing, whatever finite parameter it carries -- f(0; w) is an
+// exact zero (not 0 x Inf) and f'/d at d = 0 is finite once the kernel's NaN/Inf rule has been applied, so it only
+// multiplies x_v - x_u = 0.  The LDS-ring kernel's pair codebook (mde_ring_kernel.h, PS 3) needs it: its padding
+// lanes select a REAL value and are kept silent by reading their own dummy row as x_u.  Log1p with the exponents 1,
+// 1.5 and 2: d^e = 0, log1p(0) = 0.  (Not Log: w log(1 - exp(-0)) = -Inf.  Not a run-time exponent: d^0 = 1.)
+// mde_zero_at_zero is the one statement of the rule: the functors' trait and the host's choice of the stream form
+// (mde_ring_params.hip) both read it.
+constexpr bool mde_zero_at_zero(int kind, int kind_neg, int ecls) {
+  return kind == MDE_F_LOG1P && kind_neg == MDE_F_NONE && ecls >= 1 && ecls <= 3;
+}
 struct FnRuntime {
   static constexpr bool kFiniteG = false;
+  static constexpr bool kZeroAtZero = false;
   static constexpr bool kRingFused = false;
   static constexpr float kParamScale = 1.0f;
   MdeFuncArgs A;
@@ -359,6 +370,7 @@ struct FnRuntime {
 template <int KIND, int ECLS>
 struct FnSingle {
   static constexpr bool kFiniteG = (KIND == MDE_F_LOG1P && ECLS == 2) || KIND == MDE_F_QUADRATIC;
+  static constexpr bool kZeroAtZero = mde_zero_at_zero(KIND, MDE_F_NONE, ECLS);
   static constexpr bool kRingFused = (KIND == MDE_F_LOG1P && ECLS == 2);
   static constexpr float kParamScale = kRingFused ? 1.5f : 1.0f;
   MdeFuncArgs A;
@@ -380,6 +392,7 @@ struct FnPushPull {
   // d >= 2e-13); at d = 0 the reference's NaN / Inf -> 1 rule multiplies
   // x_v - x_u = 0 and so does this 0)
   static constexpr bool kFiniteG = kMerged;
+  static constexpr bool kZeroAtZero = false;
   static constexpr bool kRingFused = false;
   static constexpr float kParamScale = 1.0f;
   MdeFuncArgs A;

@@ -137,7 +137,11 @@ static __device__ int g_ring_ndiag;
 // PS, the form of the first parameter: 0 = an fp32 array next to the packed words (or one scalar), 1 = codebook
 // (value index in the packed word's spare bits, <= 7 / 3 values), 2 = byte index (one byte per entry beside the
 // packed words -- 5 B per half-edge --, a 256-entry value table in the 1 KB behind the ring; round 5: the hop
-// counts of a distance-preserving problem on a graph are tens of distinct integers, which streamed 8 B until now)
+// counts of a distance-preserving problem on a graph are tens of distinct integers, which streamed 8 B until now),
+// 3 = pair codebook (the codebook's 4-byte stream for arrays of ONE or TWO distinct values -- k-NN weights {1, 2}, unit
+// weights: bit 0 of the packed word selects between two wave-constant registers, a0[0] and a0[1]; no LDS table, no
+// lookup in the consumer's LDS queue.  Padding lanes select a real value too: mde_plan_expand_codebook_for points
+// their x_u at their own dummy row, so x_v - x_u = 0 and a functor with kZeroAtZero adds an exact zero)
 // MDE_RING_FWORDS (round 6): producers publish INDEPENDENTLY -- F[p] = the next chunk of producer p that has not landed --
 // and a consumer takes the minimum of the four words (one ds_read_b128, prefetched a pair ahead like round 5's single
 // word).  Round 5 published in chunk order through ONE word: a producer that has stored chunk j waits until
@@ -168,7 +172,8 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
   constexpr int dbg = 0;
 #endif
   constexpr int BS = MDE_RING_BS, NCW = MDE_RING_NCW, NPROD = MDE_RING_NPROD;
-  constexpr bool CB = PS == 1, BX = PS == 2;
+  constexpr bool CB = PS == 1, BX = PS == 2, CP = PS == 3;
+  static_assert(!CP || (Fn::kZeroAtZero && LIN && (D == 2 || D == 3)), "pair codebook: padding lanes rely on f(0; w) = 0");
   constexpr int GR_OFF = ring_gr_off(D), CTRL_PROG = MDE_RING_CTRL_PROG(D), CTRL_F = MDE_RING_CTRL_F(D), CTRL_CB = MDE_RING_CTRL_CB(D);
   constexpr int C = ring_chunk_cols(D), CBYTES = ring_chunk_bytes(D), PIECES = CBYTES / 1024;
   static_assert(GR_OFF + (ring_row_cap(D) + 32) * 4 * D <= 65536 + GR_OFF && GR_OFF < 65536 && CTRL_CB + 32 < 65536,
@@ -449,6 +454,8 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
     const int NB = (__builtin_amdgcn_readfirstlane(wave_iter[blockIdx.x * NCW + wave + 1]) - ib) >> 2;
     if (NB > 0 && !(dbg & 64)) {
       const bool a0_arr = !a0_scalar && PS == 0;
+      // (CP: the two values, scaled as the LDS table's entries are -- the same floats)
+      const float cp0 = CP ? a0[0] * Fn::kParamScale : 0.0f, cp1 = CP ? a0[1] * Fn::kParamScale : 0.0f;
       const uint32_t* bp = BX ? bidx + (size_t)(ib >> 2) * 64 + lane : nullptr;
       const ring_u4* sp = reinterpret_cast<const ring_u4*>(packed) + (size_t)(ib >> 2) * 64 + lane;
       const ring_f4* ap = reinterpret_cast<const ring_f4*>(a0_arr ? a0 : reinterpret_cast<const float*>(packed)) +
@@ -514,7 +521,13 @@ __global__ __launch_bounds__(MDE_RING_BS) void k_fused_ring(
       auto issue_x = [&](uint32_t w, float p0, uint32_t bi4) __attribute__((always_inline)) {
         Pre r;
         // (codebook index: the bits the row address leaves free -- 3 at d = 2, 2 at d = 3; byte index: bi4 = 4 x index)
-        if constexpr (BX)
+        if constexpr (CP) {
+          // bit 0 spread over the word (v_bfe_i32), then one bit select between the two registers: depends on the
+          // stream word alone, so the scheduler is free to place it where the word arrives
+          // (inline asm: written as (cp1 & m) | (cp0 & ~m) the compiler turns it into v_and + v_cmp + v_cndmask)
+          const uint32_t m = (uint32_t)((int32_t)(w << 31) >> 31);
+          asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r.p0) : "v"(m), "v"(cp1), "v"(cp0));
+        } else if constexpr (BX)
           r.p0 = *reinterpret_cast<const float*>(L + tab_off + bi4);
         else
           r.p0 = CB ? *reinterpret_cast<const float*>(L + CTRL_CB + ((w & (D == 2 ? 7u : 3u)) << 2)) : p0 * Fn::kParamScale;
@@ -1013,7 +1026,7 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_ring_combine(int64_t m, int Q, co
 template <int D, class Fn, bool LIN>
 static int launch_ring(const RingArgs& A, const Fn& fn, int* nblocks) {
   const mde_ring_layout& L = A.plan->ring;
-  const bool cb = A.a0_scalar == 2, bx = A.a0_scalar == 3;
+  const bool cp = A.a0_scalar == 4, cb = A.a0_scalar == 2 || cp, bx = A.a0_scalar == 3;
   if ((cb || bx) && D != 2 && D != 3) {
     mde_set_error("codebook / byte-index parameter streams exist for d = 2 and d = 3 only");
     return MDE_E_INVALID;
@@ -1034,8 +1047,16 @@ static int launch_ring(const RingArgs& A, const Fn& fn, int* nblocks) {
   if constexpr (D == 2 || D == 3) {
     if (cb) kern = A.grad ? k_fused_ring<D, Fn, true, 1, LIN> : k_fused_ring<D, Fn, false, 1, LIN>;
     if (bx) kern = A.grad ? k_fused_ring<D, Fn, true, 2, LIN> : k_fused_ring<D, Fn, false, 2, LIN>;
+    if constexpr (Fn::kZeroAtZero && LIN) {
+      if (cp) kern = A.grad ? k_fused_ring<D, Fn, true, 3, LIN> : k_fused_ring<D, Fn, false, 3, LIN>;
+    }
   }
-  // codebook form: a0 = [H packed words | 8 values]; byte-index form: a0 = [H index bytes | 256 values]
+  if (cp && !(Fn::kZeroAtZero && LIN && (D == 2 || D == 3))) {
+    // (mde_plan_expand_codebook_for writes this form for such functions only)
+    mde_set_error("pair-codebook parameter stream (a0_scalar = 4) with a function whose padding entries would not add zero");
+    return MDE_E_INVALID;
+  }
+  // codebook forms: a0 = [H packed words | 8 values]; byte-index form: a0 = [H index bytes | 256 values]
   const uint32_t* stream = cb ? reinterpret_cast<const uint32_t*>(A.a0) : L.packed;
   const uint32_t* bidx = bx ? reinterpret_cast<const uint32_t*>(A.a0) : nullptr;
   const float* a0 = cb ? A.a0 + L.H : (bx ? A.a0 + L.H / 4 : A.a0);

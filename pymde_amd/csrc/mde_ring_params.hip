@@ -1,6 +1,7 @@
 // mde_ring_params.hip -- per-edge parameter arrays in the order of the LDS-ring layout (layout 1): the plain fp32
-// stream, the 8-value codebook in the packed words' low bits and the 255-value byte index.  A unit of its own: these
-// kernels run when a function is bound to a plan, after the layout build and apart from it.
+// stream, the 8-value codebook in the packed words' low bits (and its two-value form, the pair codebook) and the
+// 255-value byte index.  A unit of its own: these kernels run when a function is bound to a plan, after the layout
+// build and apart from it.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -96,7 +97,12 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_codebook_scan(int64_t p, const fl
 }
 
 // out[q] = packed[q] | index of in[eid[q]] in table (padding entries keep index 0)
-__global__ __launch_bounds__(MDE_BLOCK) void k_codebook_pack(int64_t H, const uint32_t* __restrict__ packed,
+// PAIR (the pair codebook, at most two values): table[0..1] are the values and the index is ONE bit, so a padding
+// entry selects table[0] -- a real weight.  What keeps it silent is its distance: its column field is pointed at its
+// own row, a dummy row in the x_v region (resident from the prologue on, zero, never written), so x_v - x_u = 0
+// exactly and a function with kZeroAtZero adds nothing.
+template <bool PAIR>
+__global__ __launch_bounds__(MDE_BLOCK) void k_codebook_pack(int64_t H, int d, const uint32_t* __restrict__ packed,
                                                              const int32_t* __restrict__ eid,
                                                              const float* __restrict__ in,
                                                              const unsigned int* __restrict__ table,
@@ -110,9 +116,17 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_codebook_pack(int64_t H, const ui
     if (eid[q] >= 0) {
       const unsigned int v = __float_as_uint(in[eid[q]]);
       uint32_t idx = 0;
+      if (PAIR) {
+        idx = (tb[1] == v) ? 1u : 0u;  // (one value: both entries hold it, either index will do)
+      } else {
 #pragma unroll
-      for (int s = 1; s < MDE_RING_CB_VALUES; ++s) idx = (tb[s] == v) ? (uint32_t)s : idx;
+        for (int s = 1; s < MDE_RING_CB_VALUES; ++s) idx = (tb[s] == v) ? (uint32_t)s : idx;
+      }
       w |= idx;  // (padding entries keep index 0 = weight 0)
+    } else if (PAIR) {
+      // (ring_pack_word: the row address in the low half, the column address / 8 or / 4 from bit 16; d = 2 keeps
+      // its loss flag in bit 31)
+      w = d == 2 ? ((w & 0x8000ffffu) | (((w & 0xfff8u) >> 3) << 16)) : ((w & 0xffffu) | (((w & 0xfffcu) >> 2) << 16));
     }
     out[q] = w;
   }
@@ -120,13 +134,16 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_codebook_pack(int64_t H, const ui
 
 // Try to put a per-edge parameter array into codebook form for layout 1.  On success
 // (*n_values_host in 1..7 at d = 2, 1..3 at d = 3) out_half holds the H packed words with the value index
-// in their low bits, followed by the 8-entry value table; pass it as mde_func.a0 with a0_scalar = 2.
+// in their low bits, followed by the 8-entry value table; pass it as mde_func.a0 with a0_scalar = *form_host:
+// 2, or 4 -- the pair codebook -- when `f` is given, the array has one or two values and every entry of f whose two
+// ends coincide adds zero (mde_zero_at_zero; MDE_CODEBOOK_PAIR=0: never).
 // *n_values_host = 0: not applicable (another d, too many distinct values, NaNs) -- nothing is
 // written and the caller uses mde_plan_expand_layout.  SYNC.
-extern "C" int mde_plan_expand_codebook(const mde_plan* plan, const float* in_edge, float* out_half,
-                                        int32_t* n_values_host, void* stream) {
-  if (!plan || !in_edge || !out_half || !n_values_host) return MDE_E_INVALID;
+static int expand_codebook(const mde_plan* plan, const mde_func* f, const float* in_edge, float* out_half,
+                           int32_t* n_values_host, int32_t* form_host, void* stream) {
+  if (!plan || !in_edge || !out_half || !n_values_host || !form_host) return MDE_E_INVALID;
   *n_values_host = 0;
+  *form_host = 0;
   const mde_ring_layout& L = plan->ring;
   // (the index rides in the bits the row address leaves free: 3 at d = 2 -- up to 7 values --, 2 at d = 3 --
   // up to 3, enough for a neighbour graph's {1, 2, -1})
@@ -174,17 +191,36 @@ extern "C" int mde_plan_expand_codebook(const mde_plan* plan, const float* in_ed
       vals[b - 1] = t;
     }
   for (int s = nv + 1; s < MDE_RING_CB_VALUES; ++s) vals[s] = MDE_CB_EMPTY;
+  const bool pair = f && nv <= 2 && env_int("MDE_CODEBOOK_PAIR", 1) != 0 &&
+                    mde_zero_at_zero(f->kind, f->kind_neg, mde_exp_class(f->s0));
+  if (pair) {
+    // the table of the pair form: the two values a lane can select, both finite (one value: twice)
+    vals[0] = vals[1];
+    vals[1] = nv == 2 ? vals[2] : vals[1];
+    vals[2] = MDE_CB_EMPTY;
+  }
   err = hipMemcpyAsync(table, vals, sizeof(vals), hipMemcpyHostToDevice, st);
   if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_codebook_pack, dim3(mde_grid(L.H, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, L.H, L.packed,
-                       L.eid, in_edge, table, reinterpret_cast<uint32_t*>(out_half));
+    hipLaunchKernelGGL(pair ? k_codebook_pack<true> : k_codebook_pack<false>, dim3(mde_grid(L.H, MDE_BLOCK, 4096)), dim3(MDE_BLOCK),
+                       0, st, L.H, L.d, L.packed, L.eid, in_edge, table, reinterpret_cast<uint32_t*>(out_half));
     err = hipGetLastError();
   }
   const hipError_t esync = hipStreamSynchronize(st);  // `vals` is a stack buffer: wait whatever the launch said
   if (err == hipSuccess) err = esync;
   if (err != hipSuccess) return mde_hip_fail(err, "parameter codebook pack", __FILE__, __LINE__);
   *n_values_host = nv;
+  *form_host = pair ? 4 : 2;
   return MDE_OK;
+}
+extern "C" int mde_plan_expand_codebook(const mde_plan* plan, const float* in_edge, float* out_half,
+                                        int32_t* n_values_host, void* stream) {
+  int32_t form = 0;
+  return expand_codebook(plan, nullptr, in_edge, out_half, n_values_host, &form, stream);
+}
+extern "C" int mde_plan_expand_codebook_for(const mde_plan* plan, const mde_func* f, const float* in_edge, float* out_half,
+                                            int32_t* n_values_host, int32_t* form_host, void* stream) {
+  if (!f) return MDE_E_INVALID;
+  return expand_codebook(plan, f, in_edge, out_half, n_values_host, form_host, stream);
 }
 
 // ---------------------------------------------------------------- byte-index parameter streams
