@@ -604,6 +604,23 @@ int64_t mde_knn_refine_work_bytes(int64_t n, int32_t k);
 int mde_knn_refine(int64_t n, int32_t nf, const float* X, const float* sqn, int32_t k, const int32_t* idx_in,
                    const float* d2_in, const int32_t* rev, int32_t* idx_out, float* d2_out, int32_t* changed_out,
                    void* work, void* stream);
+/* Landmark selection (csrc/mde_landmarks.hip): m distinct rows of data [n, nf], chosen one after
+ * the other from every row's squared distance to its nearest landmark so far.  method 0: farthest point (the row
+ * with the largest such distance, ties to the smallest row); method 1: k-means++ (the smallest row whose inclusive
+ * prefix sum of those distances, float64 in row order, exceeds u_t * total, u_t the top 53 bits of draw t of the
+ * SplitMix64 stream of seed; the smallest unselected row when the total is 0).  Position 0 is `start`.  The
+ * distance is the float32 sum_f (x_f - l_f)^2, exactly 0 between equal rows, summed in an order fixed by nf.
+ * idx_out int32 [m]: the rows in selection order; radius2_out [m]: each one's squared distance to the landmarks
+ * before it (+inf at position 0); mind2_out [n]: every row's squared distance to its nearest landmark (0 for the
+ * landmarks); nearest_out int32 [n]: the position in idx_out of that landmark, ties to the earlier one.  mind2_out
+ * and nearest_out are also the state of the run.  work: mde_select_landmarks_work_bytes(n, nf, m) bytes.  All of it
+ * is enqueued on the stream (2 m + 1 launches, nothing is read back); the same bits on every run and for every grid.
+ * 1 <= m <= n < 2^31, 1 <= nf <= 2^30, 0 <= start < n: MDE_E_INVALID / MDE_E_TOO_LARGE otherwise (the byte count: a
+ * negative MDE_E_* code). */
+int64_t mde_select_landmarks_work_bytes(int64_t n, int32_t nf, int64_t m);
+int mde_select_landmarks(int64_t n, int32_t nf, const float* data, int64_t m, int32_t method, int64_t start,
+                         uint64_t seed, int32_t* idx_out, float* radius2_out, float* mind2_out,
+                         int32_t* nearest_out, void* work, void* stream);
 /* Sparse data matrices (SURVEY 8f rows f2 / f4 on scipy.sparse inputs) [ref: preprocess/data_matrix.py:11-178].
  * Every entry below takes one device CSR of n rows and nf columns: indptr int64 [n + 1], indices int32
  * [nnz] (column ids, strictly increasing within a row), values float32 [nnz]; n < 2^31, nf < 2^31, nnz may

@@ -123,7 +123,10 @@ SYMBOLS = {
     "mde_ann_centroids": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "mde_knn_refine_work_bytes": (c_i64, [c_i64, c_i32]),
     "mde_knn_refine": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "mde_knn_l1": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "mde_select_landmarks_work_bytes": (c_i64, [c_i64, c_i32, c_i64]),
+    "mde_select_landmarks": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, ctypes.c_uint64, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp]),
+    "mde_knn_l1":(c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mde_rows_normalize": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mde_pair_distances_metric": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "mde_sparse_rows_normalize": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

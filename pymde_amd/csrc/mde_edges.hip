@@ -13,13 +13,7 @@
 #include <vector>
 
 #include "mde_common.h"
-
-__device__ __forceinline__ uint64_t mde_splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+#include "mde_rng.h"
 
 // canonical key of an edge: (min, max) -> min * n + max
 __global__ __launch_bounds__(MDE_BLOCK) void k_edge_keys(int64_t n, int64_t p, const int64_t* __restrict__ edges,

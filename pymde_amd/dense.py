@@ -30,6 +30,7 @@ import torch
 from pymde_amd import _lib
 from pymde_amd import constraints
 from pymde_amd import graph as _graph
+from pymde_amd import landmarks as _landmarks
 from pymde_amd import metrics as _metrics
 from pymde_amd import optim
 from pymde_amd import preprocess
@@ -784,8 +785,9 @@ class LandmarkMDE(object):
     (a ``LandmarkSolveStats`` of both stages).  Score the result with ``quality.stress(data, X, sample=...)``."""
 
     def __init__(self, data, landmarks, embedding_dim=2, loss=losses.Absolute, constraint=None, metric="euclidean",
-                 seed=None, device=None, weights=None):
+                 seed=None, device=None, weights=None, selection="uniform"):
         parse_weights(weights, allow_matrix=False)
+        selection = _landmarks.resolve_selection(selection)
         metric = check_source(data, metric)
         quality._check_matrix(data, "data")
         n = int(data.shape[0])
@@ -801,7 +803,14 @@ class LandmarkMDE(object):
         self.metric = metric
         self.loss = loss
         self.weights = weights
-        self.landmarks = quality._sample_rows(n, m, seed).to(torch.int64)
+        self.selection = selection
+        self.landmark_radius = None
+        if selection == _landmarks.UNIFORM:
+            self.landmarks = quality._sample_rows(n, m, seed).to(torch.int64)
+        else:
+            chosen = _landmarks.select(data, m, method=selection, metric=metric, seed=seed, device=device)
+            self.landmarks = chosen.indices.cpu()
+            self.landmark_radius = float(chosen.distance.max())
         placed = torch.ones(n, dtype=torch.bool)
         placed[self.landmarks] = False
         self.placed = placed.nonzero().reshape(-1)

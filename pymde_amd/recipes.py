@@ -15,6 +15,7 @@ from pymde_amd import _lib
 from pymde_amd import constraints
 from pymde_amd import dense as _dense
 from pymde_amd import graph as _graph
+from pymde_amd import landmarks as _landmarks
 from pymde_amd import metrics as _metrics
 from pymde_amd import preprocess
 from pymde_amd import problem
@@ -136,7 +137,7 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
                        max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False,
-                       landmarks=None, weights=None):
+                       landmarks=None, weights=None, landmark_selection="uniform"):
     """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
@@ -160,7 +161,10 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     of O(n^2), which is how all-pairs distance preservation reaches a million rows.  ``constraint`` must be
     ``None`` or ``Centered()``: the placed rows are unconstrained, so ``Standardized`` and ``Anchored`` are a
     ``ValueError``.  ``max_distances`` is not consulted.  Score the result with
-    ``quality.stress(data, X, sample=...)``.
+    ``quality.stress(data, X, sample=...)``.  ``landmark_selection`` (with ``landmarks=m`` only): ``"uniform"`` (the
+    default, that draw), ``"farthest"`` or ``"kmeans++"``: the landmarks ``pymde_amd.landmarks.select`` chooses under
+    ``metric`` and ``seed``, which cover the data where a uniform draw follows its density; the problem's
+    ``landmark_radius`` is then their covering radius.
 
     ``weights=p`` (with ``dense=True`` or ``landmarks=m`` only): a real number ``p >= 0``; every pair is weighed by
     ``D^-p`` as ``DenseMDE(weights=p)`` does it (``loss=Quadratic, weights=1`` is Sammon mapping), in both stages of
@@ -171,9 +175,13 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
         if landmarks is None and not dense:
             raise ValueError("`weights` applies to the dense problems (dense=True or landmarks=m); the edge-list "
                              "problem is weighed through its loss, e.g. losses.WeightedQuadratic")
+    landmark_selection = _landmarks.resolve_selection(landmark_selection)
+    if landmarks is None and landmark_selection != _landmarks.UNIFORM:
+        raise ValueError("`landmark_selection` chooses the rows of the landmark path; pass landmarks=m with it")
     if landmarks is not None:
         return _dense.LandmarkMDE(data, landmarks, embedding_dim=embedding_dim, loss=loss, constraint=constraint,
-                                  metric=metric, seed=seed, device=device, weights=weights)
+                                  metric=metric, seed=seed, device=device, weights=weights,
+                                  selection=landmark_selection)
     if dense:
         return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights)
     metric = _metrics.resolve(metric)
