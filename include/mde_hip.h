@@ -647,6 +647,24 @@ int mde_sparse_distances(int64_t n, int32_t nf, int64_t nnz, const int64_t* indp
 int mde_sparse_rows_normalize(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr,
                               const int32_t* indices, const float* values, float* values_out,
                               int32_t* deg_out, void* stream);
+/* C = A B - u v^T for the CSR A [n, nf] and a dense row-major B [nf, r] float32, 1 <= r <= 256:
+ *   C[i, c] = sum over the stored entries e of row i of values[e] * B[indices[e], c]  -  u[i] * v[c],
+ * C [n, r] float32; u float32 [n] or NULL (all ones); v DOUBLE [r] or NULL (no correction).  The rank-one term
+ * centres a sparse matrix without densifying it: (A - 1 mu^T) B = A B - 1 (mu^T B); on the transposed CSR,
+ * (A - 1 mu^T)^T Q = A^T Q - mu (1^T Q).  Products and sums in float64, a row's entries in ascending column
+ * order, the correction subtracted in float64, one rounding to float32 at the store.  A row longer than
+ * mde_csr_spmm_segment() entries is cut into segments of that many entries, summed by different waves into
+ * float64 partials in `work` and added in segment order by a second launch; no atomics, the same bits on every
+ * run.  work: mde_csr_spmm_work_bytes(n, nnz, r) bytes (a bound that does not read the row pointers: two float64
+ * [r] slots per segment length of nnz; a negative MDE_E_* code for invalid sizes), need not be initialised.
+ * UNLIKE the entries above this one does NOT validate the CSR: the precondition is a canonical CSR that
+ * mde_sparse_validate accepts (the caller validates once per matrix, not once per product).  r outside
+ * [1, 256], negative sizes and NULL pointers: MDE_E_INVALID with a message, nothing launched.  ASYNC. */
+int32_t mde_csr_spmm_segment(void);
+int64_t mde_csr_spmm_work_bytes(int64_t n, int64_t nnz, int32_t r);
+int mde_csr_spmm(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                 const float* values, int32_t r, const float* B, const float* u, const double* v, float* C,
+                 void* work, void* stream);
 /* Shortest-path distances on the graph whose edges built `plan` (a FULL plan; its symmetrised CSR
  * is the adjacency) [ref: preprocess/graph.py:286-474, _graph.pyx:10-52].
  * w: per-half-edge edge lengths in plan (CSR) order (mde_plan_expand), or NULL for unit lengths

@@ -134,6 +134,9 @@ SYMBOLS = {
     "mde_sparse_validate": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_sparse_knn": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_sparse_distances": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "mde_csr_spmm_segment": (c_i32, []),
+    "mde_csr_spmm_work_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "mde_csr_spmm": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_graph_knn": (c_i32, [c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mde_graph_shortest_paths": (c_i32, [c_vp, c_vp, c_f32, ctypes.c_double, ctypes.c_uint64, c_i64,
                                          c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),

@@ -19,6 +19,7 @@ from pymde_amd import ann as _ann
 from pymde_amd import metrics as _metrics
 from pymde_amd import sparse as _sparse
 from pymde_amd import util
+from pymde_amd.pca import PrincipalComponents, principal_components  # noqa: F401  (public here)
 
 _LOGGER = logging.getLogger("__pymde_amd__")   # problem.LOGGER
 

@@ -24,6 +24,7 @@ import torch
 
 from pymde_amd import _lib
 from pymde_amd import average_distortion as _ad
+from pymde_amd import sparse as _sparse
 from pymde_amd import util
 from pymde_amd.functions import penalties
 
@@ -143,6 +144,16 @@ def _sym(A):
     return 0.5 * (A + A.T)
 
 
+def _orthonormal(ops, blocks):
+    """Orthonormal basis of the span of the given [n, *] blocks (explicit vectors): one Gram
+    matrix of the concatenated block, one right-multiplication, then one re-orthonormalisation
+    pass that removes the fp32 error of the first.  Null directions are dropped, so the result is
+    narrower than the blocks when they have lost rank.  (Shared with ``pymde_amd.pca``.)"""
+    S = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1).contiguous()
+    out = ops.rmul(S, _orthonormalizer(_sym(ops.gram(S, S))))
+    return ops.rmul(out, _orthonormalizer(ops.gram(out, out)))
+
+
 def _lobpcg(lap, k, max_iter, tol, device, scale_by_operator=False):
     """Block LOBPCG for the k smallest non-trivial eigenpairs of the Laplacian.
 
@@ -158,12 +169,7 @@ def _lobpcg(lap, k, max_iter, tol, device, scale_by_operator=False):
     ops = _Ops(n, device, 3 * k)
 
     def orthonormal(blocks):
-        """Orthonormal basis of the span of the given [n, *] blocks (explicit vectors): one Gram
-        matrix of the concatenated block, one right-multiplication, then one re-orthonormalisation
-        pass that removes the fp32 error of the first."""
-        S = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1).contiguous()
-        out = ops.rmul(S, _orthonormalizer(_sym(ops.gram(S, S))))
-        return ops.rmul(out, _orthonormalizer(ops.gram(out, out)))
+        return _orthonormal(ops, blocks)
 
     X = orthonormal([ops.center(torch.randn((n, k), device=device, dtype=torch.float32))])
     if X.shape[1] < k:
@@ -232,7 +238,17 @@ def pca(Y, embedding_dim, device=None):
     data is formed on the GPU (``mde_center`` + ``mde_gram``), its eigendecomposition (k x k,
     float64) is done on the host, and ``U = Y V S^-1`` is one ``mde_right_multiply``.  Singular
     vectors are defined up to sign; each column is oriented so that its largest-magnitude entry
-    of the right singular vector is positive."""
+    of the right singular vector is positive.
+
+    A sparse ``Y`` (scipy sparse, torch sparse COO / CSR) is never densified: the whitened scores
+    ``scores * sqrt(n) / singular_values`` of ``preprocess.principal_components`` (the randomized
+    route on the centred matrix, with its defaults) are returned, and ``embedding_dim`` must then be
+    below ``min(n, k)``."""
+    if _sparse.is_sparse(Y):
+        from pymde_amd.pca import principal_components
+        pc = principal_components(Y, embedding_dim, device=device)
+        whiten = (float(pc.scores.shape[0]) ** 0.5 / pc.singular_values).to(torch.float32)
+        return pc.scores * whiten[None, :]
     if not isinstance(Y, torch.Tensor):
         Y = torch.as_tensor(Y)
     if device is None:
@@ -243,15 +259,25 @@ def pca(Y, embedding_dim, device=None):
     if m > min(n, k):
         raise ValueError("Embedding dimension must be at most minimum dimension of Y")
     with torch.no_grad(), torch.cuda.device(device):
-        Yc = Y.detach().to(device=device, dtype=torch.float32).contiguous().clone()
-        ops = _Ops(n, device, k)
-        ops.center(Yc)
-        G = _sym(ops.gram(Yc, Yc))
-        evals, evecs = np.linalg.eigh(G)
-        order = np.argsort(evals)[::-1][:m]
-        sing = np.sqrt(np.maximum(evals[order], 0.0))
-        if np.any(sing <= 1e-12 * max(float(sing.max()), 1e-300)):
-            raise util.SolverError("pca: the centred data matrix has rank below embedding_dim")
-        V = evecs[:, order]
-        V = V * np.sign(V[np.abs(V).argmax(axis=0), np.arange(m)])[None, :]
+        ops, Yc, V, sing, _ = _centred_basis(Y, m, device)
         return ops.rmul(Yc, V * (np.sqrt(float(n)) / sing)[None, :])
+
+
+def _centred_basis(Y, m, device):
+    """The exact route shared by ``pca`` and ``preprocess.principal_components`` for a dense ``Y``:
+    ``(ops, Yc, V, sing, G)`` with ``Yc`` the centred float32 copy on ``device``, ``G`` its Gram matrix
+    (host float64), ``V`` [k, m] the top ``m`` right singular vectors with the sign rule applied and
+    ``sing`` their singular values."""
+    n, k = int(Y.shape[0]), int(Y.shape[1])
+    Yc = Y.detach().to(device=device, dtype=torch.float32).contiguous().clone()
+    ops = _Ops(n, device, k)
+    ops.center(Yc)
+    G = _sym(ops.gram(Yc, Yc))
+    evals, evecs = np.linalg.eigh(G)
+    order = np.argsort(evals)[::-1][:m]
+    sing = np.sqrt(np.maximum(evals[order], 0.0))
+    if np.any(sing <= 1e-12 * max(float(sing.max()), 1e-300)):
+        raise util.SolverError("pca: the centred data matrix has rank below embedding_dim")
+    V = evecs[:, order]
+    V = V * np.sign(V[np.abs(V).argmax(axis=0), np.arange(m)])[None, :]
+    return ops, Yc, V, sing, G

@@ -24,6 +24,7 @@ from pymde_amd import util
 from pymde_amd import quadratic
 from pymde_amd import sparse as _sparse
 from pymde_amd.functions import losses, penalties
+from pymde_amd.pca import check_arguments as _pca_check_arguments
 
 
 class EdgeGraph(object):
@@ -240,7 +241,7 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
                        repulsive_penalty=penalties.Log, constraint=None, n_neighbors=None,
                        repulsive_fraction=None, max_distance=None, init="quadratic", device=None,
                        verbose=False, seed=None, approximate_neighbors=False, metric="euclidean",
-                       neighbor_precision="float32"):
+                       neighbor_precision="float32", n_components=None):
     """An MDE problem that preserves the k-nearest-neighbour structure of a data matrix
     (rows = items) [ref: recipes.py:221-448]: k-NN graph (weights 1 / 2), optional spectral
     initialisation, uniformly sampled repulsive edges (weight -1), ``PushAndPull`` of the two
@@ -261,9 +262,26 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
 
     ``neighbor_precision`` (data matrices only): ``"bfloat16"`` builds the k-NN graph by the bfloat16
     shortlist with float32 re-ranking of ``preprocess.k_nearest_neighbors(precision="bfloat16")``; not with
-    Manhattan or ``approximate_neighbors``."""
+    Manhattan or ``approximate_neighbors``.
+
+    ``n_components`` (data matrices under the Euclidean metric only; default None: nothing changes): the k-NN
+    graph is built on the scores of ``preprocess.principal_components(data, n_components, seed=0 if seed is None
+    else seed)`` instead of the data -- the usual first step on wide sparse data, whose search otherwise costs
+    time proportional to the number of features.  The scores are a dense matrix, so the exact, the approximate
+    and the bfloat16 search all serve them.  ``max_distance`` is then in the units of the reduced space
+    (distances between rows of the scores, which are at most the distances between rows of the data).  The
+    fitted ``PrincipalComponents`` is kept on the returned problem as ``mde.principal_components``."""
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
+    if n_components is not None:
+        if is_graph:
+            raise ValueError("n_components applies to data matrices; a Graph has no columns to reduce")
+        if metric != _metrics.EUCLIDEAN:
+            raise ValueError(f"n_components needs metric='euclidean' (got '{metric}'): principal components keep "
+                             "Euclidean distances, not cosine, correlation or Manhattan ones")
+        if not hasattr(data, "shape"):
+            data = torch.as_tensor(data)
+        _pca_check_arguments(data.shape, n_components, sparse=_sparse.is_sparse(data))
     neighbor_precision = preprocess._check_precision_arguments(
         neighbor_precision, None, 1, metric, approximate_neighbors not in (None, False), is_graph)
     if is_graph:
@@ -303,6 +321,13 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
         edges, weights = _graph.k_nearest_neighbors(data, k=n_neighbors, graph_distances=True,
                                                           max_distance=max_distance, verbose=verbose)
     else:
+        fitted = None
+        if n_components is not None:
+            if verbose:
+                problem.LOGGER.info(f"Reducing the data to {n_components} principal components")
+            fitted = preprocess.principal_components(data, n_components, seed=0 if seed is None else seed,
+                                                     device=device)
+            data = fitted.scores
         if knn_options:
             knn_options.setdefault("seed", 0 if seed is None else seed)
             knn_options["verbose"] = verbose
@@ -346,6 +371,8 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     mde = problem.MDE(n_items=n, embedding_dim=embedding_dim, edges=edges, distortion_function=f,
                       constraint=constraint, device=device)
     mde._X_init = X_init
+    if n_components is not None:
+        mde.principal_components = fitted
     # overlapping points make the average distortion non-differentiable: perturb them apart
     if bool((mde.distances(mde._X_init) == 0).any()):
         mde._X_init = mde._X_init + 1e-4 * torch.randn(mde._X_init.shape, device=device,
@@ -411,7 +438,12 @@ def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repu
     ``Standardized`` does not stay standardized once new rows are added.
 
     ``neighbor_precision="bfloat16"`` takes the neighbours by
-    ``preprocess.cross_nearest_neighbors(precision="bfloat16")``."""
+    ``preprocess.cross_nearest_neighbors(precision="bfloat16")``.
+
+    Data that were reduced by principal components are extended in the reduced space, old and new rows in one
+    coordinate system: with ``pc`` the fitted ``PrincipalComponents`` (``mde.principal_components``, or the
+    result of ``preprocess.principal_components(data, 50)``),
+        ``extend_embedding(pc.scores, X, pc.transform(new_data))``."""
     metric = _metrics.resolve(metric)
     neighbor_precision = preprocess.resolve_precision(neighbor_precision)
     if metric == _metrics.MANHATTAN:
@@ -501,13 +533,14 @@ def _approximate_options(approximate_neighbors):
 
 def laplacian_embedding(data, embedding_dim=2, n_neighbors=None, max_distance=None, init="quadratic",
                         device=None, verbose=False, approximate_neighbors=False, metric="euclidean",
-                        neighbor_precision="float32"):
+                        neighbor_precision="float32", n_components=None):
     """An MDE problem whose solution is a Laplacian embedding [ref: recipes.py:451-503]: the k-NN
     graph of ``preserve_neighbors`` with quadratic penalties, no repulsion and the standardization
-    constraint.  ``data``, ``approximate_neighbors``, ``metric`` and ``neighbor_precision`` as for
-    ``preserve_neighbors``."""
+    constraint.  ``data``, ``approximate_neighbors``, ``metric``, ``neighbor_precision`` and ``n_components``
+    (the k-NN graph on that many principal components, seed 0; ``max_distance`` then in the reduced space's
+    units) as for ``preserve_neighbors``."""
     return preserve_neighbors(data, embedding_dim=embedding_dim, attractive_penalty=penalties.Quadratic,
                               repulsive_penalty=None, n_neighbors=n_neighbors, max_distance=max_distance,
                               init=init, device=device, verbose=verbose,
                               approximate_neighbors=approximate_neighbors, metric=metric,
-                              neighbor_precision=neighbor_precision)
+                              neighbor_precision=neighbor_precision, n_components=n_components)

@@ -10,6 +10,7 @@ torch inputs are canonicalised on their own device.
 import numpy as np
 import torch
 
+from pymde_amd import _lib
 from pymde_amd import util
 
 _MAX_DIM = 2 ** 31 - 1
@@ -80,6 +81,77 @@ class DeviceCSR(object):
         t = torch.sparse_csr_tensor(self.indptr, self.indices.to(torch.int64), self.values, self.shape,
                                     device=self.device)
         return t.to_dense().contiguous()
+
+    def transpose(self):
+        """The canonical CSR of the transposed matrix (``n_features`` rows, ``n`` columns, column ids
+        increasing within a row), on the device of this one -- a CPU as well: only torch is used.  A stable
+        sort of the column ids keeps the entries of a column in row order."""
+        rows = torch.repeat_interleave(torch.arange(self.n, dtype=torch.int32, device=self.device),
+                                       self.indptr[1:] - self.indptr[:-1])
+        cols = self.indices.to(torch.int64)
+        order = torch.sort(cols, stable=True).indices
+        indptr = torch.zeros(self.n_features + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(torch.bincount(cols, minlength=self.n_features), 0, out=indptr[1:])
+        return DeviceCSR(indptr, rows[order].contiguous(), self.values[order].contiguous(),
+                         (self.n_features, self.n))
+
+    def validate(self):
+        """``mde_sparse_validate`` on this matrix: an ``MdeHipError`` for a malformed CSR.  The products of
+        ``spmm`` index through the arrays unchecked, so a matrix is validated once before the first one."""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mde_sparse_validate(self.n, self.n_features, self.nnz, _lib.ptr(self.indptr),
+                                                       _lib.ptr(self.indices), _lib.ptr(self.values),
+                                                       _lib.stream_ptr(self.device)))
+        return self
+
+
+def from_dense(X):
+    """The canonical CSR of the non-zero entries of a dense float32 [n, nf] tensor, on its device (NaN and
+    infinity are kept as entries, so a finiteness check of the result sees them)."""
+    n, nf = _check_shape(X.shape)
+    mask = X != 0
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=X.device)
+    torch.cumsum(mask.sum(1), 0, out=indptr[1:])
+    cols = mask.nonzero()[:, 1].to(torch.int32).contiguous()       # row-major: ascending within a row
+    return DeviceCSR(indptr, cols, X[mask].to(torch.float32).contiguous(), (n, nf))
+
+
+def spmm_segment():
+    """The segment length of ``mde_csr_spmm``: a longer row is summed in pieces of this many entries."""
+    return int(_lib.load().mde_csr_spmm_segment())
+
+
+def spmm(csr, B, u=None, v=None, work=None):
+    """``csr @ B - outer(u, v)`` by ``mde_csr_spmm``: ``B`` float32 [n_features, r] on the GPU, ``r <= 256``;
+    ``u`` float32 [n] (None: all ones), ``v`` float64 [r] (None: no correction).  Float64 sums, one rounding;
+    returns float32 [n, r].  ``csr`` must be a valid canonical CSR (``DeviceCSR.validate``): it is not checked
+    here.  ``work``: a buffer from ``spmm_work`` to reuse across calls."""
+    lib = _lib.load()
+    if B.dim() != 2 or int(B.shape[0]) != csr.n_features:
+        raise ValueError(f"spmm: B must be [{csr.n_features}, r] (got shape {tuple(B.shape)})")
+    r = int(B.shape[1])
+    B = B.to(device=csr.device, dtype=torch.float32).contiguous()
+    if u is not None:
+        u = u.to(device=csr.device, dtype=torch.float32).contiguous()
+        if u.numel() != csr.n:
+            raise ValueError(f"spmm: u must hold {csr.n} values (got {u.numel()})")
+    if v is not None:
+        v = v.to(device=csr.device, dtype=torch.float64).contiguous()
+        if v.numel() != r:
+            raise ValueError(f"spmm: v must hold {r} values (got {v.numel()})")
+    out = torch.empty((csr.n, r), dtype=torch.float32, device=csr.device)
+    with torch.cuda.device(csr.device):
+        if work is None or work.numel() < max(int(lib.mde_csr_spmm_work_bytes(csr.n, csr.nnz, r)), 0):
+            work = spmm_work(csr, r)
+        _lib.check(lib.mde_csr_spmm(csr.n, csr.n_features, csr.nnz, _lib.ptr(csr.indptr), _lib.ptr(csr.indices),
+                                    _lib.ptr(csr.values), r, _lib.ptr(B), _lib.ptr(u), _lib.ptr(v), _lib.ptr(out),
+                                    _lib.ptr(work), _lib.stream_ptr(csr.device)))
+    return out
+
+
+def spmm_work(csr, r):
+    """The scratch buffer of ``spmm(csr, B [n_features, r])`` (``mde_csr_spmm_work_bytes``)."""
+    return _lib.work_buffer(_lib.load().mde_csr_spmm_work_bytes, csr.n, csr.nnz, int(r), device=csr.device)
 
 
 def to_device_csr(data, device=None):
