@@ -503,6 +503,30 @@ int mde_pair_loss_cross_rows_weighted(int64_t n_q, int64_t n_c, int32_t nf, cons
                                       const float* XC, int32_t kind, float s0, float s1, float s2, int32_t slices,
                                       int64_t n_rows, const int32_t* rows, int32_t wsource, float p, const float* W,
                                       double* row_loss, float* row_grad, void* work, void* stream);
+/* The product of the (never stored) matrix of SQUARED deviations with a thin block of vectors (csrc/mde_pair_apply.hip,
+ * DESIGN section 6p): the primitive of classical scaling and of distance-based triangulation (pymde_amd.classical).
+ *   out[i][k] = sum_j S(i, j) V[j][k]      i < n_q, j < n_c, k < r, 1 <= r <= 32
+ * V float32 [n_c, r] (finite), out DOUBLE [n_q, r], both row-major on the device.  S(i, j) comes from exactly one of the
+ * two sources of mde_pair_loss_cross:
+ *   Q [n_q, nf] and C [n_c, nf]   the prepared data rows, both given; with d2 = fmaxf(|x|^2 + |y|^2 - 2 x.y, 0) the Gram
+ *               tile's own squared distance (bit for bit that of mde_pair_moments): mode 0  S = d2 as it is, never
+ *               sqrtf and squared again; mode 1  S = (0.5f d2)^2, the product formed in double;
+ *   Dm [n_q, n_c]   a row-major float32 matrix of deviations, Q and C NULL: S = Dm[i][j]^2 formed in double, so the
+ *               square is exact (nf and mode are ignored; an entry equal to FLT_MAX is skipped).
+ * There is no d_scale: the product is linear, the caller scales by its square.  skip_diagonal != 0 requires n_q == n_c
+ * and leaves out j == i by index: a duplicate row elsewhere is an ordinary pair, and neither a non-zero Dm[i][i] nor the
+ * rounding noise of d2(i, i) counts.  The grid is (ceil(n_q / 64), slices), slices as in mde_pair_loss_cross (0:
+ * automatic).  Sums in double, one fma per (pair, k), in a fixed order and without floating-point atomics: the four
+ * threads of a tile row are combined in thread order and the slices are added in slice order, so for a given slice
+ * count `out` is the same bits on every run and a row's result does not depend on which rows share its block.
+ * work: mde_pair_sqdist_apply_work_bytes(n_q, n_c, r, slices) = (s > 1 ? s n_q r 8 : 0) + 4 (n_q + n_c) bytes (the
+ * per-slice partials, the row norms of Q and of C); the call allocates nothing.  Arguments are checked on the host
+ * before any launch, MDE_E_INVALID with a message: r outside [1, 32], both sources or neither, a mode other than 0 / 1,
+ * skip_diagonal with n_q != n_c, sizes outside [1, 2^31), a NULL V / out / work.  ASYNC. */
+int64_t mde_pair_sqdist_apply_work_bytes(int64_t n_q, int64_t n_c, int32_t r, int32_t slices);
+int mde_pair_sqdist_apply(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t mode,
+                          const float* Dm, int32_t skip_diagonal, int32_t r, const float* V, int32_t slices,
+                          double* out, void* work, void* stream);
 /* One pass over a weight matrix W [n_q, n_c] (square != 0: n_q == n_c, the diagonal is ignored) and, when Dm is not
  * NULL, over the deviations it weighs.  A pair is KEPT when its w > 0.
  *   counts int64 [5]   0 entries of W that are NaN or infinite | 1 entries that are negative | 2 kept pairs (square: of

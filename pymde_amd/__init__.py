@@ -18,6 +18,8 @@ from pymde_amd import quadratic  # noqa: F401
 from pymde_amd import preprocess  # noqa: F401
 from pymde_amd import quality  # noqa: F401
 from pymde_amd import landmarks  # noqa: F401
+from pymde_amd import classical  # noqa: F401
+from pymde_amd.classical import classical_mds  # noqa: F401
 from pymde_amd.graph import Graph  # noqa: F401
 from pymde_amd.quadratic import pca  # noqa: F401
 from pymde_amd.recipes import laplacian_embedding, preserve_distances, preserve_neighbors  # noqa: F401

@@ -113,6 +113,9 @@ SYMBOLS = {
     "mde_pair_loss_cross_rows_weighted": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp,
                                                   c_vp, c_i32, c_f32, c_f32, c_f32, c_i32, c_i64, c_vp, c_i32, c_f32,
                                                   c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_pair_sqdist_apply_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "mde_pair_sqdist_apply": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp,
+                                      c_vp, c_vp]),
     "mde_pair_weights_check": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_rows_init": (c_i32, [c_i64, c_i32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp]),

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from pymde_amd import _lib
+from pymde_amd import classical as _classical
 from pymde_amd import constraints
 from pymde_amd import graph as _graph
 from pymde_amd import landmarks as _landmarks
@@ -52,6 +53,16 @@ Weights.__doc__ = """The ``weights=`` of a dense problem as the kernels take it:
 ``p`` of the power form, and ``W``, the matrix of the matrix form (as it was passed, until the problem puts it on its
 device as float32)."""
 NO_WEIGHTS = Weights(W_NONE, 0.0, None)
+
+INITS = ("random", "classical")                     # the `init=` of DenseMDE and LandmarkMDE
+PLACEMENT_INITS = ("neighbors", "triangulation")    # the `init` of DensePlacement
+
+
+def check_init(init, accepted=INITS, name="init"):
+    """``init`` if it is one of ``accepted``; ``ValueError`` otherwise (no device is needed to say so)."""
+    if not isinstance(init, str) or init not in accepted:
+        raise ValueError(f"`{name}` must be one of {', '.join(repr(a) for a in accepted)}; got {init!r}")
+    return init
 
 WeightStats = collections.namedtuple("WeightStats", ["nonfinite", "negative", "kept", "empty_rows", "bad_deviations",
                                                      "asymmetry", "largest", "deviation_asymmetry",
@@ -281,15 +292,24 @@ class DenseMDE(object):
     ``1 / D^2``; every other loss is multiplied by it.  ``DenseMDE.from_graph`` builds such a problem from a
     ``Graph``'s shortest paths.
 
+    ``init``: where ``embed()`` starts when it is given no ``X``.  ``"random"`` (the default): the constraint's own
+    draw.  ``"classical"``: ``classical_initialization()``, the closed-form classical scaling of the problem's own
+    deviations (``pymde_amd.classical``); a ``ValueError`` with ``Anchored`` and when a weight
+    matrix leaves out pairs.  Power weights are ignored by the start and used by the solve.
+
     After ``embed()``: ``X``, ``solve_stats``, ``value`` and ``residual_norm``, as for ``MDE``.  The per-pair
     ``distances`` / ``distortions`` / ``high_distortion_pairs`` of ``MDE`` are n^2 values and are not provided;
     ``item_distortions`` has one value per item.  With ``Anchored`` the anchor-anchor pairs stay in the mean: they
     add a constant to the value and nothing to the gradient of the free rows."""
 
     def __init__(self, data=None, embedding_dim=2, loss=losses.Absolute, constraint=None, distance_matrix=None,
-                 metric="euclidean", deviation_scale=1.0, device=None, weights=None):
+                 metric="euclidean", deviation_scale=1.0, device=None, weights=None, init="random"):
         if (data is None) == (distance_matrix is None):
             raise ValueError("exactly one of `data` and `distance_matrix` must be given")
+        self.init = check_init(init)
+        if init == "classical" and isinstance(constraint, constraints.Anchored):
+            raise ValueError("init='classical' is not available with an Anchored constraint: classical scaling fixes "
+                             "the position of every row, the anchors' included")
         self._set_loss(int(embedding_dim), loss, deviation_scale, "embedding_dim",
                        " (the kernel keeps a row of the embedding in registers)")
         source = data if data is not None else distance_matrix
@@ -318,6 +338,10 @@ class DenseMDE(object):
         self._item_pairs = n - 1
         self.n_all_pairs = n * (n - 1) // 2
         self._set_weights(weights, True)
+        if init == "classical" and self.p != self.n_all_pairs:
+            raise ValueError(f"init='classical' needs every pair, and `weights` leaves out "
+                             f"{self.n_all_pairs - self.p} of {self.n_all_pairs} (the pairs of a disconnected graph, "
+                             "or the zeros of a weight matrix)")
         self.metric = metric if data is not None else None
         self.constraint = constraints.Centered() if constraint is None else constraint
         self._reset()
@@ -435,10 +459,31 @@ class DenseMDE(object):
                    weights=W)
 
     # ------------------------------------------------------------------ the solve
+    def classical_initialization(self, **solver_keywords):
+        """The classical start [n, d]: the classical scaling of the problem's own source and ``deviation_scale``
+        (``solver_keywords``: the ``n_oversamples``, ``n_iter``, ``seed`` and ``test_matrix`` of ``classical_mds``);
+        the columns whose eigenvalue is at most 1e-6 of the largest get ``1e-3 sqrt(lambda_1 / n)`` times standard
+        normal noise, since a flat start is a saddle of the loss; the result is projected onto the constraint."""
+        if isinstance(self.constraint, constraints.Anchored) or self.p != self.n_all_pairs:
+            raise ValueError("the classical start needs every pair and no anchors")
+        fit = _classical.scale_problem(self._A, self._mode, self._Dm, self.deviation_scale, self.embedding_dim,
+                                       **solver_keywords)
+        X = fit.X.clone()
+        lam = fit.eigenvalues
+        flat = lam <= _classical.NOISE_RTOL * lam[0]
+        if bool(flat.any()):
+            noise = 1e-3 * math.sqrt(max(float(lam[0]), 0.0) / self.n_items)
+            X[:, flat] += noise * torch.randn((self.n_items, int(flat.sum())), device=self.device,
+                                              dtype=torch.float32)
+        return self.constraint.project_onto_constraint(X.contiguous(), inplace=True)
+
     def embed(self, X=None, eps=1e-5, max_iter=300, memory_size=10, verbose=False, print_every=None,
               snapshot_every=None):
-        """Compute an embedding; stores it in ``self.X`` and returns it.  Arguments as in ``MDE.embed``."""
-        if X is None:
+        """Compute an embedding; stores it in ``self.X`` and returns it.  Arguments as in ``MDE.embed``; without
+        ``X`` the start is the one ``init`` names."""
+        if X is None and self.init == "classical":
+            X = self.classical_initialization()
+        elif X is None:
             X = self.constraint.initialization(self.n_items, self.embedding_dim, self.device)
         else:
             X = X.detach().clone()
@@ -551,7 +596,8 @@ class DensePlacement(DenseMDE):
     both spaces is an ordinary pair (D = E = 0).  ``DensePlacement.weighted(..., weights=)`` builds the same problem
     with a weight per pair, or with missing pairs.
 
-    ``embed()`` starts, by default, every new row at the mean of the embedding vectors of its ``d + 1`` nearest old
+    ``embed()`` starts every new row where ``initialization()`` puts it: by default (the attribute ``init`` is
+    ``"neighbors"``; set it, or pass ``init=`` to ``weighted``, for ``"triangulation"``) every new row at the mean of the embedding vectors of its ``d + 1`` nearest old
     rows (``d + 1`` points fix a position in R^d; perturbed by 1e-4 if a new row lands exactly on an old one).  The
     objective is separable over the new rows, and ``embed`` has two solvers for it.  ``solver="joint"`` (the default)
     runs ONE L-BFGS over all new rows: one step length and one set of curvature pairs for rows that do not interact.
@@ -568,15 +614,25 @@ class DensePlacement(DenseMDE):
 
     @classmethod
     def weighted(cls, data, X, new_data, *, weights, loss=losses.Absolute, metric="euclidean", deviation_scale=1.0,
-                 distance_matrix=None, device=None):
+                 distance_matrix=None, device=None, init="neighbors"):
         """The placement with a weight per (new row, embedded row) pair: the arguments of the constructor and
         ``weights``, as for ``DenseMDE`` -- ``None``, a number ``p`` (every pair is weighed by ``D^-p``), or a matrix
         [n_new, n_old] (no symmetry to ask for) whose zeros are MISSING pairs.  Every new row must keep a pair; ``p``
         is the number kept; a ``distance_matrix`` is then checked on its kept pairs only; with ``solver="rows"`` the
-        reported values are those of this joint problem.  (The constructor's own parameter list is fixed.)"""
+        reported values are those of this joint problem.  ``init`` sets the attribute of that name.  (The
+        constructor's own parameter list is fixed.)"""
+        check_init(init, PLACEMENT_INITS)
         self = cls.__new__(cls)
         self._setup(data, X, new_data, loss, metric, deviation_scale, distance_matrix, device, weights)
+        if init == "triangulation":
+            self._check_triangulation()
+        self.init = init
         return self
+
+    def _check_triangulation(self):
+        if self.p != self.n_all_pairs:
+            raise ValueError(f"the triangulated start needs the deviation of every (new row, embedded row) pair, and "
+                             f"`weights` leaves out {self.n_all_pairs - self.p} of {self.n_all_pairs}")
 
     def _setup(self, data, X, new_data, loss, metric, deviation_scale, distance_matrix, device, weights):
         from_data = data is not None or new_data is not None
@@ -646,6 +702,7 @@ class DensePlacement(DenseMDE):
         self.constraint = _Free()
         self._reset()
         self.row_status = None
+        self.init = "neighbors"
 
     def __str__(self):
         source = "data matrices, metric %s" % self.metric if self._A is not None else "distance matrix"
@@ -671,10 +728,17 @@ class DensePlacement(DenseMDE):
         rows (a 0-dim float32 tensor; differentiable w.r.t. ``X``)."""
         return _DenseDistortion.apply(self._embedding_arg(X), self)
 
-    def initialization(self):
-        """The default start [n_new, d]: every new row at the mean of the embedding vectors of its ``d + 1`` nearest
-        embedded rows (fewer when there are fewer), perturbed by 1e-4 if a new row lands exactly on one of
-        them."""
+    def initialization(self, method=None):
+        """The start [n_new, d] of ``embed()``; ``method`` defaults to the attribute ``init`` (``"neighbors"`` unless
+        it was set).  ``"neighbors"``: every new row at the mean of the embedding vectors of its ``d + 1`` nearest
+        embedded rows (fewer when there are fewer), perturbed by 1e-4 if a new row lands exactly on one of them.
+        ``"triangulation"``: ``classical.triangulate``, the closed-form least-squares position of every new row from
+        its squared deviations to ALL embedded rows (a ``ValueError`` when a weight matrix leaves out pairs)."""
+        method = check_init(self.init if method is None else method, PLACEMENT_INITS, "method")
+        if method == "triangulation":
+            self._check_triangulation()
+            return _classical.triangulate(self._X_old, Q=self._Q, C=self._A if self._Q is not None else None,
+                                          mode=self._mode, Dm=self._Dm, deviation_scale=self.deviation_scale)
         k = min(self.embedding_dim + 1, self.n_old)
         if self._Dm is not None and self._row_kept is not None:
             # (a missing pair's entry may be anything: it is never among the nearest)
@@ -779,14 +843,17 @@ class LandmarkMDE(object):
     ``Centered()``: the result is centred, and the placed rows can keep no other constraint.  ``seed`` draws the
     landmarks (``quality._sample_rows``): the same seed gives the same ``landmarks``.  ``weights``: ``None`` or a
     number ``p``, the power form ``D^-p`` of ``DenseMDE``, handed to both stages; a matrix is a ``ValueError``.
+    ``init``: ``"random"`` (the default) or ``"classical"``, which starts the landmarks from their classical scaling
+    and every other row from its triangulation against them (``initialization()`` returns that start).
 
     After ``embed()``: ``X`` [n, d] in the row order of ``data``, ``landmarks`` (int64 indices), ``landmark_problem``
     (the ``DenseMDE``), ``placement`` (the ``DensePlacement``), ``value`` (the placement's value) and ``solve_stats``
     (a ``LandmarkSolveStats`` of both stages).  Score the result with ``quality.stress(data, X, sample=...)``."""
 
     def __init__(self, data, landmarks, embedding_dim=2, loss=losses.Absolute, constraint=None, metric="euclidean",
-                 seed=None, device=None, weights=None, selection="uniform"):
+                 seed=None, device=None, weights=None, selection="uniform", init="random"):
         parse_weights(weights, allow_matrix=False)
+        self.init = check_init(init)
         selection = _landmarks.resolve_selection(selection)
         metric = check_source(data, metric)
         quality._check_matrix(data, "data")
@@ -818,12 +885,31 @@ class LandmarkMDE(object):
         self._landmark_data = _take_rows(data, self.landmarks)
         self.landmark_problem = DenseMDE(self._landmark_data, embedding_dim=embedding_dim, loss=loss,
                                          constraint=constraints.Centered(), metric=metric, device=device,
-                                         weights=weights)
+                                         weights=weights, init=init)
         self.device = self.landmark_problem.device
         self.placement = None
         self.X = None
         self.value = None
         self.solve_stats = None
+
+    def _placement(self, X_l):
+        return DensePlacement.weighted(self._landmark_data, X_l, _take_rows(self._data, self.placed), loss=self.loss,
+                                       metric=self.metric, device=self.device, weights=self.weights,
+                                       init="triangulation" if self.init == "classical" else "neighbors")
+
+    def initialization(self):
+        """The [n, d] start of both stages, without solving: the landmarks where their problem starts (with
+        ``init="classical"`` their classical scaling) and every other row where the placement starts against those
+        (triangulated)."""
+        problem = self.landmark_problem
+        if self.init == "classical":
+            X_l = problem.classical_initialization()
+        else:
+            X_l = problem.constraint.initialization(problem.n_items, self.embedding_dim, self.device)
+        out = torch.empty((self.n_items, self.embedding_dim), dtype=torch.float32, device=self.device)
+        out[self.landmarks.to(self.device)] = X_l
+        out[self.placed.to(self.device)] = self._placement(X_l).initialization()
+        return out
 
     def embed(self, X=None, placement_solver="joint", **solver_args):
         """Embed the landmarks, place the other rows, centre the whole: stores the [n, d] embedding in ``self.X`` and
@@ -839,9 +925,7 @@ class LandmarkMDE(object):
             X = X.detach().to(device=self.device, dtype=torch.float32)
             start_l, start_p = X[self.landmarks.to(self.device)], X[self.placed.to(self.device)]
         X_l = self.landmark_problem.embed(start_l, **solver_args)
-        self.placement = DensePlacement.weighted(self._landmark_data, X_l, _take_rows(self._data, self.placed),
-                                                 loss=self.loss, metric=self.metric, device=self.device,
-                                                 weights=self.weights)
+        self.placement = self._placement(X_l)
         X_p = self.placement.embed(start_p, solver=placement_solver, **solver_args)
         out = torch.empty((self.n_items, self.embedding_dim), dtype=torch.float32, device=self.device)
         out[self.landmarks.to(self.device)] = X_l

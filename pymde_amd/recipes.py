@@ -138,7 +138,7 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
                        max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False,
-                       landmarks=None, weights=None, landmark_selection="uniform"):
+                       landmarks=None, weights=None, landmark_selection="uniform", init="random"):
     """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
@@ -170,7 +170,15 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     ``weights=p`` (with ``dense=True`` or ``landmarks=m`` only): a real number ``p >= 0``; every pair is weighed by
     ``D^-p`` as ``DenseMDE(weights=p)`` does it (``loss=Quadratic, weights=1`` is Sammon mapping), in both stages of
     the landmark path.  A weight matrix is a ``ValueError`` here: build the ``DenseMDE`` directly.  The edge-list
-    path takes its weights through the loss (``WeightedQuadratic``)."""
+    path takes its weights through the loss (``WeightedQuadratic``).
+
+    ``init`` (with ``dense=True`` or ``landmarks=m`` only): ``"random"`` (the default) or ``"classical"``, the
+    ``init`` of ``DenseMDE`` and ``LandmarkMDE``: ``embed()`` then starts from the classical scaling of the
+    deviations (and, on the landmark path, from the triangulation of the other rows against the landmarks)."""
+    _dense.check_init(init)
+    if init != "random" and landmarks is None and not dense:
+        raise ValueError("`init` applies to the dense problems (dense=True or landmarks=m); the edge-list problem "
+                         "starts where its constraint's initialization puts it (pass embed(X=...) for another start)")
     if weights is not None:
         _dense.parse_weights(weights, allow_matrix=False)
         if landmarks is None and not dense:
@@ -182,9 +190,10 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     if landmarks is not None:
         return _dense.LandmarkMDE(data, landmarks, embedding_dim=embedding_dim, loss=loss, constraint=constraint,
                                   metric=metric, seed=seed, device=device, weights=weights,
-                                  selection=landmark_selection)
+                                  selection=landmark_selection, init=init)
     if dense:
-        return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights)
+        return _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights,
+                                         init)
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
     if is_graph:
@@ -215,7 +224,8 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
                        device=edges.device)
 
 
-def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights=None):
+def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights=None,
+                              init="random"):
     """``preserve_distances(dense=True)``: the ``DenseMDE`` over every pair of the rows of ``data``."""
     metric = _dense.check_source(data, metric)
     if not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
@@ -234,7 +244,7 @@ def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, ver
         rms = (moments.sum_dd / moments.count) ** 0.5
         deviation_scale = float(constraint.natural_length(n_items, embedding_dim)) / rms
     return _dense.DenseMDE(data, embedding_dim=embedding_dim, loss=loss, constraint=constraint, metric=metric,
-                           deviation_scale=deviation_scale, device=device, weights=weights)
+                           deviation_scale=deviation_scale, device=device, weights=weights, init=init)
 
 
 def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p,
