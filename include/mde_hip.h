@@ -704,6 +704,36 @@ int mde_graph_shortest_paths(const mde_plan* plan, const float* w, float max_len
  * mde_edges_count_unique drops [ref: preprocess/data_matrix.py:147-175]. */
 int mde_knn_pairs(int64_t n, int32_t k, const int32_t* idx, const float* val, float max_value,
                   int64_t* pairs_out, void* stream);
+/* Per-row calibration of edge affinities over directed neighbour lists.  idx [n, k] int32
+ * (-1 = empty slot), val [n, k] float32, 1 <= k <= 64, n k < 2^31 - 1.  An entry is MISSING when its idx is
+ * outside [0, n) or equals its row, or when has_max != 0 and !(val <= max_value) (the rule of mde_knn_pairs);
+ * the others are the row's k_i kept entries, at distance d = scale * (root ? sqrt(max(val, 0)) : val) formed in
+ * double (scale > 0).
+ *   kind 0, perplexity > 0: s_j = d_j^2 - min_j d_j^2, p_j = exp(-beta s_j) / sum, beta >= 0 the root of
+ *     -sum p log p = log(perplexity).  c = #{s_j = 0}.  perplexity >= k_i or c == k_i: p = 1 / k_i, beta = 0;
+ *     perplexity <= c: 1 / c on the entries with s_j = 0 and 0 elsewhere, beta = +inf.  bandwidth = beta,
+ *     offset = min_j d_j.
+ *   kind 1 (UMAP's smooth k-NN distances; perplexity is not read): rho = the smallest positive d_j (0 when
+ *     there is none), g_j = max(d_j - rho, 0), p_j = exp(-g_j / sigma), sigma the root of sum_j p_j = log2(k_i),
+ *     then raised to at least 1e-3 * mean_j d_j.  c = #{g_j = 0}.  c == k_i: all ones (sigma = that floor);
+ *     log2(k_i) <= c: the root is the limit sigma -> 0, so sigma = the floor and p_j = exp(-g_j / floor).
+ *     bandwidth = sigma, offset = rho.
+ * Roots by bisection in double until the bracket is below 2^-48 of its upper end (at most 400 steps); sums in a
+ * fixed order; one rounding to float32 per output.  idx_out [n, k] = idx with -1 at every missing entry, p_out
+ * [n, k] (0 at missing entries), bandwidth_out [n], offset_out [n]; a row with k_i = 0 writes zeros.  The same
+ * bits on every run.  ASYNC. */
+int mde_knn_calibrate(int64_t n, int32_t k, const int32_t* idx, const float* val, int32_t root, double scale,
+                      int32_t has_max, float max_value, int32_t kind, double perplexity, int32_t* idx_out,
+                      float* p_out, float* bandwidth_out, float* offset_out, void* stream);
+/* Undirected edges of directed neighbour lists with combined weights.  idx [n, k] (the idx_out above: -1 =
+ * no entry; the kept entries of a row distinct and none of them the row itself), p [n, k] float32.  For the
+ * edge {i, j}, i < j: a = p[i][slot of j] (0 when i does not list j), b the same from row j;
+ *   rule 0 (mean): w = 0.5f * (a + b) in float32;   rule 1 (union): w = (float)(a + b - a b) in double.
+ * edges_out [>= n k, 2] int64 and weights_out [>= n k] receive each edge once, i < j, sorted by (i, j): the
+ * edge set and order of mde_knn_pairs + mde_edges_count_unique on the same lists (an edge whose weight is 0
+ * stays).  *count_host = their number.  n k < 2^31 - 1.  SYNC. */
+int mde_knn_symmetrize(int64_t n, int32_t k, const int32_t* idx, const float* p, int32_t rule,
+                       int64_t* edges_out, float* weights_out, int64_t* count_host, void* stream);
 /* k nearest neighbours of every vertex under the graph's shortest-path metric (direct = 0) or among
  * its graph neighbours by edge length (direct = 1) [ref: preprocess/graph.py:502-587].  plan / w /
  * max_length as for mde_graph_shortest_paths.  idx_out [n, k] int32 (-1 = fewer than k targets

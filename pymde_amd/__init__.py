@@ -17,6 +17,7 @@ from pymde_amd.util import align, all_edges, center, rotate, seed  # noqa: F401
 from pymde_amd import quadratic  # noqa: F401
 from pymde_amd import preprocess  # noqa: F401
 from pymde_amd import quality  # noqa: F401
+from pymde_amd import affinity  # noqa: F401
 from pymde_amd import landmarks  # noqa: F401
 from pymde_amd import classical  # noqa: F401
 from pymde_amd.classical import classical_mds  # noqa: F401

@@ -134,6 +134,9 @@ SYMBOLS = {
     "mde_pair_distances_metric": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "mde_sparse_rows_normalize": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_knn_pairs": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    "mde_knn_calibrate": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_i32, ctypes.c_double, c_i32, c_f32, c_i32,
+                                  ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_knn_symmetrize": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_sparse_validate": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_sparse_knn": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_sparse_distances": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),

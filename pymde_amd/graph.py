@@ -165,6 +165,13 @@ def k_nearest_neighbors(graph, k, graph_distances=False, max_distance=None, verb
     neighbours, 1 otherwise.  Ties in distance go to the smaller node index (the reference's
     ``argsort`` leaves them unspecified)."""
     from pymde_amd import preprocess
+    idx, dist = _neighbor_lists(graph, k, graph_distances=graph_distances, max_distance=max_distance)
+    return preprocess._neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, dist, None, idx.device)
+
+
+def _neighbor_lists(graph, k, graph_distances=False, max_distance=None):
+    """The list-producing half of ``k_nearest_neighbors``: ``(idx [n, k] int32, dist [n, k] float32)``, each row
+    ascending, -1 where a node has fewer than k targets within ``max_distance`` (the kernel applies the bound)."""
     if not isinstance(graph, Graph):
         raise ValueError("`graph` must be a pymde_amd.Graph instance.")
     lib = _lib.load()
@@ -185,4 +192,4 @@ def k_nearest_neighbors(graph, k, graph_distances=False, max_distance=None, verb
                                      float(max_distance) if max_distance is not None else 0.0,
                                      0 if graph_distances else 1, k, _lib.ptr(idx), _lib.ptr(dist),
                                      _lib.stream_ptr(device)))
-    return preprocess._neighbor_lists_to_graph(n, k, idx, dist, None, device)
+    return idx, dist

@@ -234,6 +234,21 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     line, say -- lose recall.  A sparse matrix is served when it is densified; one that would stay on the
     sparse kernel is an error.  ``verbose=True`` logs a recall@k estimated on 1 000 sampled rows against the
     float32 search."""
+    idx, values, bound, _, _ = _neighbor_lists(data, k, max_distance, device, graph_distances, approximate, n_lists,
+                                               n_probe, seed, verbose, metric, precision, n_candidates, n_refine)
+    return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
+
+
+def _neighbor_lists(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,
+                    n_lists=None, n_probe=None, seed=0, verbose=False, metric="euclidean",
+                    precision="float32", n_candidates=None, n_refine=0):
+    """The list-producing half of ``k_nearest_neighbors`` (same arguments, same errors): the directed neighbour
+    lists of whichever search serves ``data``, ``(idx [n, k] int32, values [n, k] float32, bound, root, scale)``.
+    ``idx`` holds -1 in an empty slot; an entry with ``values > bound`` (``bound`` is ``max_distance`` in the
+    units of ``values``, None without one or when the search applied it itself) does not count; the metric's
+    distance of an entry is ``scale * (sqrt(values) if root else values)``: ``(True, 1.0)`` for the Euclidean
+    searches, which rank by the squared distance, ``(False, 0.5)`` for cosine and correlation (the squared
+    chord of the unit rows), ``(False, 1.0)`` for Manhattan and for a ``Graph``."""
     metric = _metrics.resolve(metric)
     _metrics.check_approximate(metric, approximate)
     precision = _check_precision_arguments(precision, n_candidates, k, metric, approximate, _is_graph(data))
@@ -246,12 +261,12 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
         if approximate:
             raise ValueError("approximate=True applies to data matrices; a Graph has no approximate search")
         from pymde_amd import graph as _graph
-        return _graph.k_nearest_neighbors(data, k, graph_distances=graph_distances,
-                                          max_distance=max_distance)
+        idx, dist = _graph._neighbor_lists(data, k, graph_distances=graph_distances, max_distance=max_distance)
+        return idx, dist, None, False, 1.0
     if metric != _metrics.EUCLIDEAN:
         idx, values, bound = _metric_knn_lists(data, k, metric, max_distance, device, approximate, n_lists,
                                                n_probe, seed, verbose, precision, n_candidates, n_refine)
-        return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
+        return idx, values, bound, False, 1.0 if metric == _metrics.MANHATTAN else 0.5
     if _sparse.is_sparse(data):
         csr = _sparse.to_device_csr(data, device)
         k = _clamp_k(k, csr.n)
@@ -274,7 +289,7 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
             _check_finite_csr(csr)
             idx, d2 = _sparse_knn_lists(csr, k)
         max_d2 = None if max_distance is None else float(max_distance) ** 2
-        return _neighbor_lists_to_graph(csr.n, k, idx, d2, max_d2, csr.device)
+        return idx, d2, max_d2, True, 1.0
     if not isinstance(data, torch.Tensor):
         data = torch.as_tensor(data)
     if device is None:
@@ -288,7 +303,7 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     idx, d2 = _euclidean_knn_lists(data, k, approximate, n_lists, n_probe, seed, verbose, precision, n_candidates,
                                    n_refine)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
-    return _neighbor_lists_to_graph(n, k, idx, d2, max_d2, device)
+    return idx, d2, max_d2, True, 1.0
 
 
 _BF16_SPARSE_DOES_NOT_FIT = (

@@ -12,6 +12,7 @@ shortest-path metric for graphs, row f3) and the spectral initialiser; ``laplaci
 import torch
 
 from pymde_amd import _lib
+from pymde_amd import affinity as _affinity
 from pymde_amd import constraints
 from pymde_amd import dense as _dense
 from pymde_amd import graph as _graph
@@ -251,7 +252,7 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
                        repulsive_penalty=penalties.Log, constraint=None, n_neighbors=None,
                        repulsive_fraction=None, max_distance=None, init="quadratic", device=None,
                        verbose=False, seed=None, approximate_neighbors=False, metric="euclidean",
-                       neighbor_precision="float32", n_components=None):
+                       neighbor_precision="float32", n_components=None, weights=None):
     """An MDE problem that preserves the k-nearest-neighbour structure of a data matrix
     (rows = items) [ref: recipes.py:221-448]: k-NN graph (weights 1 / 2), optional spectral
     initialisation, uniformly sampled repulsive edges (weight -1), ``PushAndPull`` of the two
@@ -280,7 +281,18 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     time proportional to the number of features.  The scores are a dense matrix, so the exact, the approximate
     and the bfloat16 search all serve them.  ``max_distance`` is then in the units of the reduced space
     (distances between rows of the scores, which are at most the distances between rows of the data).  The
-    fitted ``PrincipalComponents`` is kept on the returned problem as ``mde.principal_components``."""
+    fitted ``PrincipalComponents`` is kept on the returned problem as ``mde.principal_components``.
+
+    ``weights`` (default None: the 1 / 2 weights, nothing changes): ``"perplexity"``, ``"umap"`` or a dict
+    ``{"kind": .., "perplexity": .., "symmetrize": ..}`` weighs the attractive edges by the distances of the
+    neighbour lists instead (``pymde_amd.affinity``): every row's kernel is calibrated to the perplexity (default
+    ``n_neighbors / 3``) or, for umap, to ``log2(k)``, and the two directions of an edge are combined by
+    ``symmetrize`` (``"mean"`` or ``"union"``; default mean for perplexity, union for umap).  The edges are those
+    of the default; their weights are the symmetrised affinities times the one factor that makes their sum equal
+    the number of directed list entries that count -- the sum of the 1 / 2 weights -- so that attraction keeps its
+    balance against the -1 repulsive edges.  The factor is taken before any ``Anchored`` edge removal.  The
+    ``affinity.Calibration`` is kept on the returned problem as ``mde.neighbor_calibration``."""
+    affinity_spec = _affinity.parse_weights(weights)
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
     if n_components is not None:
@@ -327,7 +339,11 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
         max_distance = (3 * torch.quantile(data.distances.float().cpu(), 0.75)).item()
     if verbose:
         problem.LOGGER.info(f"Computing {n_neighbors}-nearest neighbors, with max_distance={max_distance}")
-    if is_graph:
+    calibration = None
+    if is_graph and affinity_spec is not None:
+        edges, weights, calibration = _neighbor_affinities(affinity_spec, data, n_neighbors, max_distance,
+                                                           graph_distances=True)
+    elif is_graph:
         edges, weights = _graph.k_nearest_neighbors(data, k=n_neighbors, graph_distances=True,
                                                           max_distance=max_distance, verbose=verbose)
     else:
@@ -346,8 +362,12 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
         if neighbor_precision != preprocess.FLOAT32:
             knn_options["precision"] = neighbor_precision
             knn_options["verbose"] = verbose
-        edges, weights = preprocess.k_nearest_neighbors(data, k=n_neighbors, max_distance=max_distance,
-                                                        device=device, **knn_options)
+        if affinity_spec is not None:
+            edges, weights, calibration = _neighbor_affinities(affinity_spec, data, n_neighbors, max_distance,
+                                                               device=device, **knn_options)
+        else:
+            edges, weights = preprocess.k_nearest_neighbors(data, k=n_neighbors, max_distance=max_distance,
+                                                            device=device, **knn_options)
     if isinstance(constraint, constraints.Anchored):
         edges, weights = _remove_anchor_anchor_edges(edges, weights, constraint.anchors)
     if init == "quadratic":
@@ -383,11 +403,28 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     mde._X_init = X_init
     if n_components is not None:
         mde.principal_components = fitted
+    if calibration is not None:
+        mde.neighbor_calibration = calibration
     # overlapping points make the average distortion non-differentiable: perturb them apart
     if bool((mde.distances(mde._X_init) == 0).any()):
         mde._X_init = mde._X_init + 1e-4 * torch.randn(mde._X_init.shape, device=device,
                                                        dtype=mde._X_init.dtype)
     return mde
+
+
+def _neighbor_affinities(spec, data, k, max_distance, **search):
+    """``(edges, weights, calibration)`` of ``affinity.neighbor_affinities`` for a parsed ``weights=`` value, the
+    weights times the factor that makes their float64 sum the number of list entries that count."""
+    kind, perplexity, rule = spec
+    found = _affinity.neighbor_affinities(data, k, kind, perplexity=perplexity, symmetrize=rule,
+                                          max_distance=max_distance, **search)
+    n_entries = int((found.calibration.idx >= 0).sum())
+    total = float(found.weights.double().sum())
+    if not total > 0.0:
+        raise ValueError("weights: the affinities of the neighbour lists sum to zero (no neighbour within "
+                         "max_distance?)")
+    weights = (found.weights.double() * (n_entries / total)).to(torch.float32)
+    return found.edges, weights, found.calibration
 
 
 def _sample_new_item_edges(n_old, n_new, count, exclude, generator, device):
@@ -543,14 +580,15 @@ def _approximate_options(approximate_neighbors):
 
 def laplacian_embedding(data, embedding_dim=2, n_neighbors=None, max_distance=None, init="quadratic",
                         device=None, verbose=False, approximate_neighbors=False, metric="euclidean",
-                        neighbor_precision="float32", n_components=None):
+                        neighbor_precision="float32", n_components=None, weights=None):
     """An MDE problem whose solution is a Laplacian embedding [ref: recipes.py:451-503]: the k-NN
     graph of ``preserve_neighbors`` with quadratic penalties, no repulsion and the standardization
     constraint.  ``data``, ``approximate_neighbors``, ``metric``, ``neighbor_precision`` and ``n_components``
     (the k-NN graph on that many principal components, seed 0; ``max_distance`` then in the reduced space's
-    units) as for ``preserve_neighbors``."""
+    units) and ``weights`` (perplexity or UMAP affinities in place of the 1 / 2 weights) as for
+    ``preserve_neighbors``."""
     return preserve_neighbors(data, embedding_dim=embedding_dim, attractive_penalty=penalties.Quadratic,
                               repulsive_penalty=None, n_neighbors=n_neighbors, max_distance=max_distance,
                               init=init, device=device, verbose=verbose,
                               approximate_neighbors=approximate_neighbors, metric=metric,
-                              neighbor_precision=neighbor_precision, n_components=n_components)
+                              neighbor_precision=neighbor_precision, n_components=n_components, weights=weights)
