@@ -964,6 +964,22 @@ int mde_turn_enqueue(mde_turn_desc* T, int32_t cur, float t_prev, double f0, dou
 int mde_turn_wait(mde_turn_desc* T, int32_t cur, double f0, int32_t allow_next, double c1, double c2,
                   double eps_pre, double* out, void* stream);
 
+/* ---- weighted isotonic regression (csrc/mde_isotonic.hip) ----
+ * out = the nondecreasing sequence that minimises sum_i w_i (y_i - out_i)^2, 0 <= p <= 2^31 - 2 (p = 0: nothing
+ * is done).  y finite, w finite and > 0 (NULL: all ones); the caller checks that.  The fit is the left slope of
+ * the lower convex hull of the p + 1 points (sum w, sum w (y - ybar)) in double, built by a merge tree over leaves
+ * of mde_isotonic_leaf() points: every loop runs at most that many or 32 times whatever the data, nothing
+ * spins or waits between workgroups, no atomics; the same bits on every run.  `out` is nondecreasing exactly and
+ *   max |out - exact| <= 2^-23 max|y| + 2^-47 (sum_i w_i |y_i|) / min_i w_i.
+ * With N = p + 1 points, V = ceil(N / leaf) leaves and up(b) = b rounded up to a multiple of 256, `work` holds
+ *   256 + 2 up(8 N) + 2 up(4 N) + 2 up(4 V) + up(8 ceil(V / 2)) + 163840 bytes
+ * (W and S in double, two hull buffers, two node-count rows, the tangents of a level, the partial sums of the
+ * scans): about 24 bytes a value.  `out` doubles as the buffer of block starts.  ASYNC on `stream`; allocates
+ * nothing and reads nothing back. */
+int32_t mde_isotonic_leaf(void);
+int64_t mde_isotonic_work_bytes(int64_t p);   /* < 0: an MDE_E_* code */
+int mde_isotonic(int64_t p, const float* y, const float* w, float* out, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,9 @@ from pymde_amd import quality  # noqa: F401
 from pymde_amd import affinity  # noqa: F401
 from pymde_amd import landmarks  # noqa: F401
 from pymde_amd import classical  # noqa: F401
+from pymde_amd import isotonic  # noqa: F401
+from pymde_amd import ordinal  # noqa: F401
+from pymde_amd.ordinal import OrdinalMDE  # noqa: F401
 from pymde_amd.classical import classical_mds  # noqa: F401
 from pymde_amd.graph import Graph  # noqa: F401
 from pymde_amd.quadratic import pca  # noqa: F401

@@ -182,6 +182,9 @@ SYMBOLS = {
     "mde_turn_enqueue": (c_i32, [c_vp, c_i32, c_f32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp]),
     "mde_turn_wait": (c_i32, [c_vp, c_i32, ctypes.c_double, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              c_vp, c_vp]),
+    "mde_isotonic_leaf": (c_i32, []),
+    "mde_isotonic_work_bytes": (c_i64, [c_i64]),
+    "mde_isotonic": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

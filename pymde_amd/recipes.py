@@ -18,6 +18,7 @@ from pymde_amd import dense as _dense
 from pymde_amd import graph as _graph
 from pymde_amd import landmarks as _landmarks
 from pymde_amd import metrics as _metrics
+from pymde_amd import ordinal as _ordinal
 from pymde_amd import preprocess
 from pymde_amd import problem
 from pymde_amd import quality
@@ -139,7 +140,7 @@ def _remove_anchor_anchor_edges(edges, data, anchors):
 
 def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=None,
                        max_distances=5e7, device=None, verbose=False, seed=None, metric="euclidean", dense=False,
-                       landmarks=None, weights=None, landmark_selection="uniform", init="random"):
+                       landmarks=None, weights=None, landmark_selection="uniform", init="random", ordinal=False):
     """An MDE problem that preserves the pairwise distances (Euclidean by default) of a data matrix
     (rows = items) [ref: recipes.py:103-218].  At most ``max_distances`` pairs are used, sampled
     uniformly; with ``Standardized()`` the distances are rescaled to the constraint's natural
@@ -175,7 +176,15 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
 
     ``init`` (with ``dense=True`` or ``landmarks=m`` only): ``"random"`` (the default) or ``"classical"``, the
     ``init`` of ``DenseMDE`` and ``LandmarkMDE``: ``embed()`` then starts from the classical scaling of the
-    deviations (and, on the landmark path, from the triangulation of the other rows against the landmarks)."""
+    deviations (and, on the landmark path, from the triangulation of the other rows against the landmarks).
+
+    ``ordinal=True`` (the edge-list path only) returns a ``pymde_amd.OrdinalMDE`` over the same edges and deviations:
+    non-metric MDS, which uses the order of the deviations and not their values (``pymde_amd.ordinal``); ``loss``
+    must then be unweighted.  With ``dense=True``, ``landmarks=`` or an ``Anchored`` constraint it is a
+    ``ValueError``."""
+    if ordinal and (dense or landmarks is not None or isinstance(constraint, constraints.Anchored)):
+        raise ValueError("`ordinal=True` applies to the edge-list path without anchors: not with dense=True, "
+                         "landmarks=m or an Anchored constraint")
     _dense.check_init(init)
     if init != "random" and landmarks is None and not dense:
         raise ValueError("`init` applies to the dense problems (dense=True or landmarks=m); the edge-list problem "
@@ -213,6 +222,9 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     else:
         graph = distances(data, retain_fraction=retain_fraction, seed=seed, device=device, metric=metric)
     edges, deviations = graph.edges, graph.distances
+    if ordinal:
+        return _ordinal.OrdinalMDE(n_items, embedding_dim, edges, deviations, loss=loss, constraint=constraint,
+                                   device=edges.device)
     if constraint is None:
         constraint = constraints.Centered()
     elif isinstance(constraint, constraints._Standardized):
