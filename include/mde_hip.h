@@ -275,11 +275,13 @@ int mde_plan_loss_double(const mde_plan* plan, double* dst, void* stream);
 /* ------------------------------------------------------------------ edge-list preprocessing
  *  [ref: pymde/preprocess/preprocess.py:11-129]
  * De-duplicate an edge list: rows are put in (min, max) order and the unique rows are written to
- * edges_out [>= p, 2] sorted by (i, j) -- np.unique(axis=0)'s order; *count_host = their number. SYNC. */
+ * edges_out [>= p, 2] sorted by (i, j) -- np.unique(axis=0)'s order; *count_host = their number.  An item
+ * outside [0, n) is MDE_E_INVALID with a message naming the first such row (here, in mde_edges_count_unique and
+ * in the `exclude` list of mde_sample_edges): its key min * n + max would be another edge's.  SYNC. */
 int mde_edges_deduplicate(int64_t n, int64_t p, const int64_t* edges, int64_t* edges_out,
                           int64_t* count_host, void* stream);
-/* Unique edges (i < j, sorted) with their multiplicity as a float weight; rows with i == j or a
- * negative index are dropped.  This is how the k-NN graph gets weight 2 on mutual neighbours
+/* Unique edges (i < j, sorted) with their multiplicity as a float weight; rows with i == j or an
+ * item equal to -1 (an empty slot) are dropped, any other item outside [0, n) is MDE_E_INVALID.  This is how the k-NN graph gets weight 2 on mutual neighbours
  * [ref: preprocess/data_matrix.py:141-178, graph.py:51-72].  SYNC. */
 int mde_edges_count_unique(int64_t n, int64_t p, const int64_t* edges, int64_t* edges_out,
                            float* weights_out, int64_t* count_host, void* stream);
@@ -743,7 +745,10 @@ int mde_graph_knn(const mde_plan* plan, const float* w, float max_length, int32_
 /* Sample at most num_edges distinct edges i < j uniformly at random from the edges NOT in
  * `exclude` [n_exclude, 2] (NULL / 0: no exclusion); edges_out must hold num_edges rows, sorted by
  * (i, j); *count_host = number written (== num_edges unless the complement is nearly exhausted).
- * Same `seed` -> same edges.  SYNC. */
+ * Same `seed` -> same edges.  Rounds of draws (draw t of a round's seed: mde_rng.h; pair index -> edge:
+ * mde_tri_index.h) are de-duplicated and filtered until num_edges survive; a surplus is thinned at random, by the
+ * rank splitmix64(salt(seed) ^ key); a round that would draw at least C(n, 2) times offers every pair once, so
+ * a request on a small n is an exactly uniform subset and never falls short.  SYNC. */
 int mde_sample_edges(int64_t n, int64_t num_edges, uint64_t seed, const int64_t* exclude,
                      int64_t n_exclude, int64_t* edges_out, int64_t* count_host, void* stream);
 

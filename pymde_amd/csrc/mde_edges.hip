@@ -10,20 +10,27 @@
 // reference uses (preprocess.py:64-69).  Output is sorted by (i, j) -- np.unique's order.
 #include <hipcub/hipcub.hpp>
 
-#include <vector>
-
 #include "mde_common.h"
 #include "mde_rng.h"
+#include "mde_tri_index.h"
 
-// canonical key of an edge: (min, max) -> min * n + max
+#define EDGES_NO_BAD_ROW 0x7fffffff
+
+// canonical key of an edge: (min, max) -> min * n + max.  The key only names the edge when both items lie in
+// [0, n): the smallest index of a row with an item outside [lowest, n) is min-reduced into *bad_row (an integer
+// atomic: order-free; p < 2^31 - 1).  lowest is 0, or -1 where -1 marks an empty slot that the caller drops.
 __global__ __launch_bounds__(MDE_BLOCK) void k_edge_keys(int64_t n, int64_t p, const int64_t* __restrict__ edges,
-                                                         uint64_t* __restrict__ keys) {
+                                                         int64_t lowest, uint64_t* __restrict__ keys,
+                                                         int* __restrict__ bad_row) {
+  int bad = EDGES_NO_BAD_ROW;
   for (int64_t k = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; k < p;
        k += (int64_t)gridDim.x * MDE_BLOCK) {
     const longlong2 e = reinterpret_cast<const longlong2*>(edges)[k];
     const int64_t a = e.x < e.y ? e.x : e.y, b = e.x < e.y ? e.y : e.x;
     keys[k] = (uint64_t)a * (uint64_t)n + (uint64_t)b;
+    if ((a < lowest || b >= n) && (int)k < bad) bad = (int)k;   // (k ascends per thread: the first one sticks)
   }
+  if (bad != EDGES_NO_BAD_ROW) atomicMin(bad_row, bad);
 }
 
 __global__ __launch_bounds__(MDE_BLOCK) void k_keys_to_edges(int64_t n, int64_t m, const uint64_t* __restrict__ keys,
@@ -39,25 +46,18 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_keys_to_edges(int64_t n, int64_t 
 // draw t -> uniform index in [0, C(n,2)) -> edge (u < v) by the triangular bijection
 //   u = n - 2 - floor(sqrt(-8 idx + 4 n (n-1) - 7) / 2 - 1/2),
 //   v = idx + u + 1 - n(n-1)/2 + (n-u)(n-u-1)/2                     (preprocess.py:64-69)
-// evaluated in integers with a +-1 correction of the double-precision square root.
-__global__ __launch_bounds__(MDE_BLOCK) void k_sample_keys(int64_t n, int64_t draws, uint64_t seed,
+// evaluated in integers with a correction of the double-precision square root (mde_tri_index.h).
+__global__ __launch_bounds__(MDE_BLOCK) void k_sample_keys(int64_t n, int64_t draws, uint64_t seed, int enumerate,
                                                            uint64_t* __restrict__ keys) {
   const uint64_t total = (uint64_t)n * (uint64_t)(n - 1) / 2;
   for (int64_t t = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; t < draws;
        t += (int64_t)gridDim.x * MDE_BLOCK) {
-    // 64 random bits -> index by multiply-shift (bias < total / 2^64)
+    // 64 random bits -> index by multiply-shift (bias < total / 2^64); enumerate: every pair once instead
     const uint64_t r = mde_splitmix64(seed ^ mde_splitmix64((uint64_t)t));
-    const uint64_t idx = __umul64hi(r, total);  // floor(r * total / 2^64)
-    // row u: largest u with off(u) = u n - u (u+1)/2 <= idx
-    const double disc = 4.0 * (double)n * (double)(n - 1) - 8.0 * (double)idx - 7.0;
-    int64_t u = (int64_t)n - 2 - (int64_t)floor(sqrt(disc) / 2.0 - 0.5);
-    if (u < 0) u = 0;
-    if (u > n - 2) u = n - 2;
-    auto off = [n](int64_t uu) { return (uint64_t)uu * (uint64_t)n - (uint64_t)uu * (uint64_t)(uu + 1) / 2; };
-    while (u > 0 && off(u) > idx) --u;
-    while (u < n - 2 && off(u + 1) <= idx) ++u;
-    const uint64_t v = idx - off(u) + (uint64_t)u + 1;
-    keys[t] = (uint64_t)u * (uint64_t)n + v;
+    const uint64_t idx = enumerate ? (uint64_t)t : __umul64hi(r, total);  // floor(r * total / 2^64)
+    int64_t u, v;
+    (void)mde_tri_index(n, idx, &u, &v);
+    keys[t] = (uint64_t)u * (uint64_t)n + (uint64_t)v;
   }
 }
 
@@ -78,6 +78,14 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_not_excluded(int64_t cnt, const u
     }
     flags[k] = (lo < m && excl[lo] == key) ? 0 : 1;
   }
+}
+
+// ranks[k] = splitmix64(salt ^ keys[k]): the order in which a surplus of sampled keys is thinned
+__global__ __launch_bounds__(MDE_BLOCK) void k_thin_ranks(int64_t cnt, const uint64_t* __restrict__ keys, uint64_t salt,
+                                                          uint64_t* __restrict__ ranks) {
+  for (int64_t k = (int64_t)blockIdx.x * MDE_BLOCK + threadIdx.x; k < cnt;
+       k += (int64_t)gridDim.x * MDE_BLOCK)
+    ranks[k] = mde_splitmix64(salt ^ keys[k]);
 }
 
 static int bits_for_key(uint64_t maxval) {
@@ -124,7 +132,11 @@ static int sort_unique(uint64_t* keys, int64_t cnt, uint64_t max_key, uint64_t* 
 }
 
 static int check_sizes(int64_t n, int64_t p) {
-  if (n < 2 || p < 0) return MDE_E_INVALID;
+  if (n < 2 || p < 0) {
+    mde_set_error("edge preprocessing needs n >= 2 items and a non-negative number of edges (n=%lld, edges=%lld)",
+                  (long long)n, (long long)p);
+    return MDE_E_INVALID;
+  }
   if (p >= ((int64_t)1 << 31) - 1 || n >= ((int64_t)1 << 31)) {
     mde_set_error("edge preprocessing supports up to 2^31 - 1 edges and n < 2^31");
     return MDE_E_TOO_LARGE;
@@ -132,11 +144,38 @@ static int check_sizes(int64_t n, int64_t p) {
   return MDE_OK;
 }
 
+// keys[k] = key of row k of `edges` [p, 2] (p > 0), after checking every item against [lowest, n): the key
+// min * n + max of a row outside that range would be the key of another edge (n = 10: (0, 15) -> (1, 5); a negative
+// item wraps through uint64_t), so such a list is refused with MDE_E_INVALID naming `what` and its first bad row,
+// as the reference refuses it when it builds its (n, n) matrix.  SYNC.
+static int edge_keys_checked(int64_t n, int64_t p, const int64_t* edges, int64_t lowest, uint64_t* keys,
+                             const char* what, hipStream_t st) {
+  DevBuf bad;
+  int first = EDGES_NO_BAD_ROW;
+  MDE_HIP(bad.alloc(sizeof(int)));
+  MDE_HIP(hipMemcpyAsync(bad.p, &first, sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_edge_keys, dim3(mde_grid(p, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, p, edges, lowest,
+                     keys, bad.as<int>());
+  MDE_LAUNCH_CHECK();
+  MDE_HIP(hipMemcpyAsync(&first, bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  MDE_HIP(hipStreamSynchronize(st));
+  if (first == EDGES_NO_BAD_ROW) return MDE_OK;
+  int64_t row[2] = {0, 0};
+  MDE_HIP(hipMemcpyAsync(row, edges + 2 * (int64_t)first, sizeof(row), hipMemcpyDeviceToHost, st));
+  MDE_HIP(hipStreamSynchronize(st));
+  mde_set_error("%s: row %d is (%lld, %lld), which is not a pair of items in [%lld, %lld)", what, first,
+                (long long)row[0], (long long)row[1], (long long)lowest, (long long)n);
+  return MDE_E_INVALID;
+}
+
 // edges_out [>= p, 2] receives the unique edges with i < j, sorted by (i, j); *count_host their
 // number.  Self edges are kept as (i, i) like np.unique would.  SYNC.
 extern "C" int mde_edges_deduplicate(int64_t n, int64_t p, const int64_t* edges, int64_t* edges_out,
                                      int64_t* count_host, void* stream) {
-  if (!edges_out || !count_host || (p > 0 && !edges)) return MDE_E_INVALID;
+  if (!edges_out || !count_host || (p > 0 && !edges)) {
+    mde_set_error("mde_edges_deduplicate: invalid arguments (non-null edges / edges_out / count_host)");
+    return MDE_E_INVALID;
+  }
   int rc = check_sizes(n, p);
   if (rc != MDE_OK) return rc;
   hipStream_t st = mde_stream(stream);
@@ -145,9 +184,8 @@ extern "C" int mde_edges_deduplicate(int64_t n, int64_t p, const int64_t* edges,
   DevBuf keys, uniq;
   MDE_HIP(keys.alloc(p * sizeof(uint64_t)));
   MDE_HIP(uniq.alloc(p * sizeof(uint64_t)));
-  hipLaunchKernelGGL(k_edge_keys, dim3(mde_grid(p, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, p, edges,
-                     keys.as<uint64_t>());
-  MDE_LAUNCH_CHECK();
+  rc = edge_keys_checked(n, p, edges, 0, keys.as<uint64_t>(), "mde_edges_deduplicate", st);
+  if (rc != MDE_OK) return rc;
   int64_t m = 0;
   rc = sort_unique(keys.as<uint64_t>(), p, (uint64_t)n * (uint64_t)n, uniq.as<uint64_t>(), &m, st);
   if (rc != MDE_OK) return rc;
@@ -161,7 +199,8 @@ extern "C" int mde_edges_deduplicate(int64_t n, int64_t p, const int64_t* edges,
 
 // Unique edges (i < j, sorted by (i, j)) with their multiplicity as a float weight: duplicated
 // edges have their unit weights summed, as Graph.from_edges does [ref: preprocess/graph.py:51-72,
-// data_matrix.py:170-178] (a mutual k-NN pair gets weight 2).  Rows with i == j are dropped.  SYNC.
+// data_matrix.py:170-178] (a mutual k-NN pair gets weight 2).  Rows with i == j and rows that hold -1 (an empty
+// slot) are dropped; any other item outside [0, n) is MDE_E_INVALID.  SYNC.
 __global__ __launch_bounds__(MDE_BLOCK) void k_runs_to_edges(int64_t n, int64_t m, const uint64_t* __restrict__ keys,
                                                              const int32_t* __restrict__ counts,
                                                              int64_t* __restrict__ edges, float* __restrict__ w) {
@@ -184,7 +223,10 @@ __global__ __launch_bounds__(MDE_BLOCK) void k_flag_valid_pairs(int64_t p, const
 
 extern "C" int mde_edges_count_unique(int64_t n, int64_t p, const int64_t* edges, int64_t* edges_out,
                                       float* weights_out, int64_t* count_host, void* stream) {
-  if (!edges_out || !weights_out || !count_host || (p > 0 && !edges)) return MDE_E_INVALID;
+  if (!edges_out || !weights_out || !count_host || (p > 0 && !edges)) {
+    mde_set_error("mde_edges_count_unique: invalid arguments (non-null edges / edges_out / weights_out / count_host)");
+    return MDE_E_INVALID;
+  }
   int rc = check_sizes(n, p);
   if (rc != MDE_OK) return rc;
   hipStream_t st = mde_stream(stream);
@@ -195,9 +237,8 @@ extern "C" int mde_edges_count_unique(int64_t n, int64_t p, const int64_t* edges
   MDE_HIP(kept.alloc(p * sizeof(uint64_t)));
   MDE_HIP(flags.alloc(p));
   MDE_HIP(num.alloc(sizeof(int64_t)));
-  hipLaunchKernelGGL(k_edge_keys, dim3(mde_grid(p, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, p, edges,
-                     keys.as<uint64_t>());
-  MDE_LAUNCH_CHECK();
+  rc = edge_keys_checked(n, p, edges, -1, keys.as<uint64_t>(), "mde_edges_count_unique (-1 marks an empty slot)", st);
+  if (rc != MDE_OK) return rc;
   hipLaunchKernelGGL(k_flag_valid_pairs, dim3(mde_grid(p, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, p, edges,
                      flags.as<uint8_t>());
   MDE_LAUNCH_CHECK();
@@ -243,8 +284,11 @@ extern "C" int mde_edges_count_unique(int64_t n, int64_t p, const int64_t* edges
 // [n_exclude, 2] (may be NULL).  edges_out must hold num_edges rows.  SYNC.
 extern "C" int mde_sample_edges(int64_t n, int64_t num_edges, uint64_t seed, const int64_t* exclude,
                                 int64_t n_exclude, int64_t* edges_out, int64_t* count_host, void* stream) {
-  if (!edges_out || !count_host || num_edges < 0 || n_exclude < 0 || (n_exclude > 0 && !exclude))
+  if (!edges_out || !count_host || num_edges < 0 || n_exclude < 0 || (n_exclude > 0 && !exclude)) {
+    mde_set_error("mde_sample_edges: invalid arguments (num_edges >= 0, n_exclude >= 0, non-null edges_out / "
+                  "count_host, non-null exclude when n_exclude > 0)");
     return MDE_E_INVALID;
+  }
   int rc = check_sizes(n, num_edges + num_edges / 16 + 1024);
   if (rc == MDE_OK) rc = check_sizes(n, n_exclude);
   if (rc != MDE_OK) return rc;
@@ -263,9 +307,8 @@ extern "C" int mde_sample_edges(int64_t n, int64_t num_edges, uint64_t seed, con
   if (n_exclude > 0) {
     MDE_HIP(ekeys.alloc(n_exclude * sizeof(uint64_t)));
     MDE_HIP(euniq.alloc(n_exclude * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_edge_keys, dim3(mde_grid(n_exclude, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n,
-                       n_exclude, exclude, ekeys.as<uint64_t>());
-    MDE_LAUNCH_CHECK();
+    rc = edge_keys_checked(n, n_exclude, exclude, 0, ekeys.as<uint64_t>(), "mde_sample_edges: exclude", st);
+    if (rc != MDE_OK) return rc;
     rc = sort_unique(ekeys.as<uint64_t>(), n_exclude, (uint64_t)n * (uint64_t)n, euniq.as<uint64_t>(), &me, st);
     if (rc != MDE_OK) return rc;
   }
@@ -279,11 +322,15 @@ extern "C" int mde_sample_edges(int64_t n, int64_t num_edges, uint64_t seed, con
     const double keep_frac = 1.0 - ((double)n_exclude + (double)have) / all_edges;
     int64_t draws = (int64_t)((double)need / (keep_frac > 0.05 ? keep_frac : 0.05) * 1.02) + 1024;
     if (draws > ((int64_t)1 << 30)) draws = (int64_t)1 << 30;
+    // no more pairs than draws (small n; every request has 1024 spare draws): offer every pair once instead, so
+    // that the round cannot miss a pair and the random thinning below picks among all eligible ones
+    const int enumerate = all_edges <= (double)draws;
+    if (enumerate) draws = (int64_t)all_edges;
     DevBuf keys, uniq, flags, kept, num;
     MDE_HIP(keys.alloc((size_t)(draws + have) * sizeof(uint64_t)));
     MDE_HIP(uniq.alloc((size_t)(draws + have) * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_sample_keys, dim3(mde_grid(draws, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n,
-                       draws, seed + 0x632BE59BD9B4E019ull * (uint64_t)(round + 1), keys.as<uint64_t>());
+    hipLaunchKernelGGL(k_sample_keys, dim3(mde_grid(draws, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, n, draws,
+                       seed + 0x632BE59BD9B4E019ull * (uint64_t)(round + 1), enumerate, keys.as<uint64_t>());
     MDE_LAUNCH_CHECK();
     int64_t mu = 0;
     rc = sort_unique(keys.as<uint64_t>(), draws, (uint64_t)n * (uint64_t)n, uniq.as<uint64_t>(), &mu, st);
@@ -312,30 +359,29 @@ extern "C" int mde_sample_edges(int64_t n, int64_t num_edges, uint64_t seed, con
     int64_t total = 0;
     rc = sort_unique(kept.as<uint64_t>(), mk + have, (uint64_t)n * (uint64_t)n, uniq.as<uint64_t>(), &total, st);
     if (rc != MDE_OK) return rc;
-    // keep at most num_edges: a uniformly random subset would need a shuffle; a prefix of the
-    // sorted keys would bias towards small i.  Surplus keys are thinned by stride instead.
+    // keep at most num_edges: a prefix of the sorted keys would favour small i, and dropping keys at fixed ranks of
+    // the sorted list (as this did) leaves one key near each fixed quantile of the (i, j) order when the surplus is
+    // most of the list -- every small request draws at least 1024 keys.  The surplus is thinned at random instead:
+    // every key gets the rank splitmix64(salt ^ key), the num_edges keys of smallest rank stay (the radix sort is
+    // stable, so equal ranks fall in key order) and are sorted by key again.  Still a pure function of
+    // (n, num_edges, exclude, seed).
     if (total > num_edges) {
-      // total is only slightly above num_edges: drop every ceil(total/(total-num_edges))-th key
-      // by recompacting with a flag kernel (host computes the stride)
-      DevBuf f2, k2, n2;
-      MDE_HIP(f2.alloc(total));
+      DevBuf ranks, ranks2, k2, t3;
+      MDE_HIP(ranks.alloc((size_t)total * sizeof(uint64_t)));
+      MDE_HIP(ranks2.alloc((size_t)total * sizeof(uint64_t)));
       MDE_HIP(k2.alloc((size_t)total * sizeof(uint64_t)));
-      MDE_HIP(n2.alloc(sizeof(int64_t)));
-      const int64_t drop = total - num_edges;
-      // flag = 0 for the indices floor(j * total / drop), j = 0..drop-1
-      std::vector<uint8_t> hf((size_t)total, 1);
-      for (int64_t j = 0; j < drop; ++j) hf[(size_t)(((double)j + 0.5) * (double)total / (double)drop)] = 0;
-      MDE_HIP(hipMemcpyAsync(f2.p, hf.data(), (size_t)total, hipMemcpyHostToDevice, st));
-      MDE_HIP(hipStreamSynchronize(st));
+      hipLaunchKernelGGL(k_thin_ranks, dim3(mde_grid(total, MDE_BLOCK, 4096)), dim3(MDE_BLOCK), 0, st, total,
+                         uniq.as<uint64_t>(), mde_splitmix64(seed ^ 0xD1B54A32D192ED03ull), ranks.as<uint64_t>());
+      MDE_LAUNCH_CHECK();
       size_t tb3 = 0;
-      MDE_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb3, uniq.as<uint64_t>(), f2.as<uint8_t>(), k2.as<uint64_t>(),
-                                            n2.as<int64_t>(), (int)total, st));
-      DevBuf t3;
+      MDE_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb3, ranks.as<uint64_t>(), ranks2.as<uint64_t>(),
+                                                 uniq.as<uint64_t>(), k2.as<uint64_t>(), (int)total, 0, 64, st));
       MDE_HIP(t3.alloc(tb3));
-      MDE_HIP(hipcub::DeviceSelect::Flagged(t3.p, tb3, uniq.as<uint64_t>(), f2.as<uint8_t>(), k2.as<uint64_t>(),
-                                            n2.as<int64_t>(), (int)total, st));
-      MDE_HIP(hipMemcpyAsync(acc.p, k2.p, (size_t)num_edges * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-      MDE_HIP(hipStreamSynchronize(st));
+      MDE_HIP(hipcub::DeviceRadixSort::SortPairs(t3.p, tb3, ranks.as<uint64_t>(), ranks2.as<uint64_t>(),
+                                                 uniq.as<uint64_t>(), k2.as<uint64_t>(), (int)total, 0, 64, st));
+      int64_t m2 = 0;
+      rc = sort_unique(k2.as<uint64_t>(), num_edges, (uint64_t)n * (uint64_t)n, acc.as<uint64_t>(), &m2, st);
+      if (rc != MDE_OK) return rc;
       have = num_edges;
     } else {
       MDE_HIP(hipMemcpyAsync(acc.p, uniq.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));

@@ -87,6 +87,13 @@ class Graph(object):
         if n_items is None:
             n_items = int(edges.max().item()) + 1
         n_items = int(n_items)
+        # the key below only names an edge whose items lie in [0, n_items): with n_items = 10 the row (0, 15)
+        # would come back as (1, 5) [ref: the reference fails to build its (n, n) matrix]
+        outside = ((edges < 0) | (edges >= n_items)).any(dim=1)
+        if bool(outside.any()):
+            row = int(outside.nonzero()[0])
+            raise ValueError(f"edges reference items outside [0, n_items): row {row} is "
+                             f"({int(edges[row, 0])}, {int(edges[row, 1])}) and n_items is {n_items}")
         if weights is None:
             weights = torch.ones(edges.shape[0], dtype=torch.float32, device=device)
         else:

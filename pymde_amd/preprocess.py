@@ -90,8 +90,18 @@ def _edges_on_device(edges, device=None):
     return edges.to(device=device, dtype=torch.int64).contiguous(), device
 
 
+def _check_edge_call(rc):
+    """``_lib.check`` for the edge-list functions: what they refuse as invalid -- an item outside ``[0, n_items)``
+    above all, with a message naming the first such row -- is a ``ValueError``, as in the reference (which fails to
+    build its ``(n, n)`` matrix there)."""
+    if rc == _lib.MDE_E_INVALID:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc)
+
+
 def deduplicate_edges(edges, n_items=None):
-    """Unique edges with ``e[0] <= e[1]``, sorted lexicographically [ref: preprocess.py:116-129]."""
+    """Unique edges with ``e[0] <= e[1]``, sorted lexicographically [ref: preprocess.py:116-129].  ``ValueError``
+    for a negative item or one that is not below ``n_items``."""
     edges, device = _edges_on_device(edges)
     p = edges.shape[0]
     if p == 0:
@@ -102,15 +112,17 @@ def deduplicate_edges(edges, n_items=None):
     count = ctypes.c_int64(0)
     lib = _lib.load()
     with torch.cuda.device(device):
-        _lib.check(lib.mde_edges_deduplicate(n, p, _lib.ptr(edges), _lib.ptr(out), ctypes.byref(count),
-                                             _lib.stream_ptr(device)))
+        _check_edge_call(lib.mde_edges_deduplicate(n, p, _lib.ptr(edges), _lib.ptr(out), ctypes.byref(count),
+                                                   _lib.stream_ptr(device)))
     return out[:count.value]
 
 
 def sample_edges(n, num_edges, exclude=None, seed=None, device=None):
     """Randomly sample ``num_edges`` distinct edges (i < j), none of them in ``exclude``
     [ref: preprocess.py:11-80].  The result may hold fewer rows when the complement of
-    ``exclude`` is almost exhausted."""
+    ``exclude`` is almost exhausted (never when ``n`` is so small that the sampler enumerates the pairs:
+    ``C(n, 2) <= 1.02 num_edges / (share of eligible pairs) + 1024``).  ``ValueError`` for an item of ``exclude``
+    outside ``[0, n)``: its key would be another edge's."""
     n, num_edges = int(n), int(num_edges)
     ex = None
     if exclude is not None:
@@ -130,9 +142,9 @@ def sample_edges(n, num_edges, exclude=None, seed=None, device=None):
     count = ctypes.c_int64(0)
     lib = _lib.load()
     with torch.cuda.device(device):
-        _lib.check(lib.mde_sample_edges(n, num_edges, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                        _lib.ptr(ex), n_excluded, _lib.ptr(out), ctypes.byref(count),
-                                        _lib.stream_ptr(device)))
+        _check_edge_call(lib.mde_sample_edges(n, num_edges, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                              _lib.ptr(ex), n_excluded, _lib.ptr(out), ctypes.byref(count),
+                                              _lib.stream_ptr(device)))
     return out[:count.value]
 
 
