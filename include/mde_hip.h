@@ -662,6 +662,11 @@ int mde_sparse_validate(int64_t n, int32_t nf, int64_t nnz, const int64_t* indpt
 int mde_sparse_knn(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
                    const float* values, int32_t k, int32_t* idx_out, float* d2_out, float* sqn_work,
                    void* stream);
+/* The number of feature columns per window of mde_sparse_knn(k) on a matrix of nf columns: the search walks
+ * a row's stored entries one window at a time, 64 entries per step, so a row with 64 or more entries inside
+ * one window takes more than one step there.  A multiple of 8.  Host only, nothing is launched.  k outside
+ * [1, 64] or nf < 1: MDE_E_INVALID with a message. */
+int32_t mde_sparse_knn_window(int32_t k, int32_t nf);
 /* out[e] = ||x_i - x_j|| for every edge (i, j) of edges [p, 2] (int64), summed over the union of the two
  * rows' columns as (a - b)^2 in double -- no cancellation, near-duplicate rows come out near zero.  An
  * endpoint outside [0, n) gives NaN.  Reproducible from run to run.  SYNC (the validation). */

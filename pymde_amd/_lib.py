@@ -139,6 +139,7 @@ SYMBOLS = {
     "mde_knn_symmetrize": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_sparse_validate": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mde_sparse_knn": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mde_sparse_knn_window": (c_i32, [c_i32, c_i32]),
     "mde_sparse_distances": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "mde_csr_spmm_segment": (c_i32, []),
     "mde_csr_spmm_work_bytes": (c_i64, [c_i64, c_i64, c_i32]),

@@ -288,10 +288,21 @@ static int spk_window(int k, int nf, size_t* lds_bytes) {
   const int topk = SPK_Q * k * 8;
   int W = ((80 * 1024 - topk) / (SPK_Q * 4)) & ~7;
   if (W < SPK_MIN_W) W = ((160 * 1024 - topk) / (SPK_Q * 4)) & ~7;
-  const int need = (nf + 7) & ~7;
-  if (need < W) W = need < SPK_MIN_W ? SPK_MIN_W : need;
+  if (nf < W) {                                    // (nf + 7 is formed only here: nf may be 2^31 - 1)
+    const int need = (nf + 7) & ~7;
+    if (need < W) W = need < SPK_MIN_W ? SPK_MIN_W : need;
+  }
   *lds_bytes = (size_t)W * SPK_Q * 4 + (size_t)topk;
   return W;
+}
+
+extern "C" int32_t mde_sparse_knn_window(int32_t k, int32_t nf) {
+  if (k <= 0 || k > KNN_MAXK || nf <= 0) {
+    mde_set_error("mde_sparse_knn_window: invalid arguments (1 <= k <= %d, nf >= 1)", KNN_MAXK);
+    return MDE_E_INVALID;
+  }
+  size_t lds = 0;
+  return spk_window(k, nf, &lds);
 }
 
 extern "C" int mde_sparse_knn(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,

@@ -121,6 +121,15 @@ def spmm_segment():
     return int(_lib.load().mde_csr_spmm_segment())
 
 
+def knn_window(k, nf):
+    """The number of feature columns per window of the sparse k-NN kernel at ``k`` neighbours on a matrix of
+    ``nf`` columns (``mde_sparse_knn_window``): a row's stored entries are walked one window at a time."""
+    W = int(_lib.load().mde_sparse_knn_window(int(k), int(nf)))
+    if W < 0:
+        _lib.check(W)
+    return W
+
+
 def spmm(csr, B, u=None, v=None, work=None):
     """``csr @ B - outer(u, v)`` by ``mde_csr_spmm``: ``B`` float32 [n_features, r] on the GPU, ``r <= 256``;
     ``u`` float32 [n] (None: all ones), ``v`` float64 [r] (None: no correction).  Float64 sums, one rounding;
