@@ -747,6 +747,19 @@ int mde_knn_symmetrize(int64_t n, int32_t k, const int32_t* idx, const float* p,
  * within max_length), dist_out [n, k] ascending; ties go to the smaller index.  SYNC. */
 int mde_graph_knn(const mde_plan* plan, const float* w, float max_length, int32_t direct, int32_t k,
                   int32_t* idx_out, float* dist_out, void* stream);
+/* Shortest-path lengths from a list of source nodes to every node.  plan, w and max_length as
+ * for mde_graph_shortest_paths; sources [m] int64 (device or host memory): node indices in any order, repeats
+ * allowed.  out [n, m] float32, one row per node: out[v * m + b] is the length from sources[b] to v, 0 at the source,
+ * +inf where no path exists or none of length <= max_length.  Every value is the minimum over paths of the float32
+ * left-to-right sum of the edge lengths from the source, so the bits do not depend on the run or the grid and equal
+ * those of mde_graph_shortest_paths for the pair.  MDE_E_INVALID (nothing launched) for a sharded plan, NULL
+ * pointers, m < 1 or a source outside [0, n); MDE_E_INVALID also when n sweeps do not reach the fixed point
+ * (negative lengths).  Work memory: 16 n ceil(m / 4096) + 4 n bytes.  SYNC. */
+int mde_graph_distances_from(const mde_plan* plan, const float* w, float max_length, int64_t m,
+                             const int64_t* sources, float* out, void* stream);
+/* What the calling thread's last mde_graph_distances_from did: stats[0] sweeps, [1] tiles (a node x 64 consecutive
+ * columns) relaxed over all sweeps, [2] tiles per sweep, [3] nodes handled by the many-wave kernel. */
+int mde_graph_distances_stats(int64_t* stats);
 /* Sample at most num_edges distinct edges i < j uniformly at random from the edges NOT in
  * `exclude` [n_exclude, 2] (NULL / 0: no exclusion); edges_out must hold num_edges rows, sorted by
  * (i, j); *count_host = number written (== num_edges unless the complement is nearly exhausted).

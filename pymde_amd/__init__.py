@@ -28,3 +28,4 @@ from pymde_amd.graph import Graph  # noqa: F401
 from pymde_amd.quadratic import pca  # noqa: F401
 from pymde_amd.recipes import laplacian_embedding, preserve_distances, preserve_neighbors  # noqa: F401
 from pymde_amd.recipes import extend_embedding  # noqa: F401
+from pymde_amd.recipes import preserve_geodesics  # noqa: F401

@@ -848,7 +848,10 @@ class LandmarkMDE(object):
 
     After ``embed()``: ``X`` [n, d] in the row order of ``data``, ``landmarks`` (int64 indices), ``landmark_problem``
     (the ``DenseMDE``), ``placement`` (the ``DensePlacement``), ``value`` (the placement's value) and ``solve_stats``
-    (a ``LandmarkSolveStats`` of both stages).  Score the result with ``quality.stress(data, X, sample=...)``."""
+    (a ``LandmarkSolveStats`` of both stages).  Score the result with ``quality.stress(data, X, sample=...)``.
+
+    ``LandmarkMDE.from_graph(graph, landmarks, ...)`` is the same problem on a ``Graph`` under its shortest-path
+    metric; this constructor refuses a ``Graph``."""
 
     def __init__(self, data, landmarks, embedding_dim=2, loss=losses.Absolute, constraint=None, metric="euclidean",
                  seed=None, device=None, weights=None, selection="uniform", init="random"):
@@ -892,7 +895,109 @@ class LandmarkMDE(object):
         self.value = None
         self.solve_stats = None
 
+    @classmethod
+    def from_graph(cls, graph, landmarks, embedding_dim=2, loss=losses.Absolute, constraint=None, seed=None,
+                   selection="uniform", init="random", max_length=None, weights=None):
+        """Landmark MDS on a ``Graph`` under its shortest-path metric (Landmark Isomap when the graph is a k-NN
+        graph, ``preprocess.neighbor_graph``): one ``graph.distances_from(graph, landmarks)`` call gives the lengths
+        ``D`` [n, m] from the ``landmarks`` chosen nodes to every node; the landmark stage is a ``DenseMDE`` on the
+        m x m block of ``D`` (made symmetric by the element-wise minimum of the two directions, which are both lengths
+        of real paths and can differ in the last bit), the placement stage a ``DensePlacement`` of every other node
+        against its row of ``D``.  O(n m) memory, never n^2.
+
+        A (node, landmark) pair that no path joins (of length at most ``max_length``, if given) is MISSING, not
+        infinitely far: both stages then get a zero/one weight matrix, as ``DenseMDE.from_graph`` builds one (only
+        then: it doubles the memory).  A node joined to no landmark has no position and is a ``ValueError``.
+        ``selection``: ``"uniform"`` or ``"farthest"`` (``landmarks.select_graph``: every component gets a landmark
+        before any gets a second one); ``"kmeans++"`` is a ``ValueError`` on a graph.  ``init="classical"`` needs
+        every pair.  ``weights``: ``None`` or a number ``p`` (the power form), and only when no pair is missing, since
+        the reachability mask then takes the matrix slot.  Everything else as for ``LandmarkMDE``, whose attributes
+        and ``embed()`` these are; ``metric`` is ``None``."""
+        check_init(init)
+        return cls._build_from_graph(graph, landmarks, embedding_dim, loss, constraint, seed, selection, init,
+                                     max_length, weights)
+
+    @classmethod
+    def _build_from_graph(cls, graph, landmarks, embedding_dim, loss, constraint, seed, selection, init, max_length,
+                          weights):
+        """``from_graph``; ``init=None`` (``preserve_geodesics``) is "classical" when every (node, landmark) pair is
+        joined and "random" otherwise, with one logged line saying why."""
+        parsed = parse_weights(weights, allow_matrix=False)
+        selection = _landmarks.resolve_selection(selection)
+        if selection == _landmarks.KMEANSPP:
+            raise ValueError("selection='kmeans++' draws by squared distances to the rows of a data matrix; on a Graph "
+                             "the selections are 'uniform' and 'farthest'")
+        if not isinstance(graph, _graph.Graph):
+            raise ValueError("`graph` must be a pymde_amd.Graph instance.")
+        n = int(graph.n_items)
+        m = check_landmarks(landmarks, n, constraint)
+        embedding_dim = int(embedding_dim)
+        if not 1 <= embedding_dim <= MAX_DIM:
+            raise ValueError(f"embedding_dim must lie in [1, {MAX_DIM}] for a dense problem, got {embedding_dim}")
+        loss_spec(loss)
+        if seed is None:
+            seed = int(util.np_rng().integers(0, 2 ** 63 - 1))
+        self = cls.__new__(cls)
+        self.n_items, self.embedding_dim, self.metric, self.loss = n, embedding_dim, None, loss
+        self.weights, self.selection, self.landmark_radius = weights, selection, None
+        if selection == _landmarks.UNIFORM:
+            self.landmarks = quality._sample_rows(n, m, seed).to(torch.int64)
+        else:
+            chosen = _landmarks.select_graph(graph, m, seed=seed, max_length=max_length)
+            self.landmarks = chosen.indices.cpu()
+            self.landmark_radius = float(chosen.distance.max())
+        placed = torch.ones(n, dtype=torch.bool)
+        placed[self.landmarks] = False
+        self.placed = placed.nonzero().reshape(-1)
+        D = _graph.distances_from(graph, self.landmarks, max_length=max_length)
+        device = D.device
+        joined = torch.isfinite(D)
+        others = joined.sum(dim=1)
+        others[self.landmarks.to(device)] -= 1           # (a landmark's own column does not place it)
+        stranded = int((others == 0).sum())
+        if stranded:
+            raise ValueError(f"{stranded} of the {n} nodes are joined to no landmark but themselves (no path"
+                             + (f" of length at most {max_length}" if max_length is not None else "")
+                             + " reaches them from any of the chosen nodes): such a node has no position; use more "
+                             "landmarks or selection='farthest', which visits every component first")
+        missing = int(joined.numel() - int(joined.sum()))
+        if missing and parsed.source != W_NONE:
+            raise ValueError(f"`weights`={weights!r} cannot be combined with missing pairs: {missing} (node, landmark) "
+                             "pairs of this graph are joined by no path, and the zero/one mask that leaves them out "
+                             "takes the place of the weight matrix")
+        if init is None:
+            init = "random" if missing else "classical"
+            if missing:
+                _problem.LOGGER.info(f"init='random': {missing} of the {n * m} (node, landmark) pairs are joined by no "
+                                     "path, and the classical start needs every pair")
+        elif init == "classical" and missing:
+            raise ValueError(f"init='classical' needs every pair, and {missing} of the {n * m} (node, landmark) pairs "
+                             "of this graph are joined by no path")
+        self.init = init
+        at = self.landmarks.to(device)
+        block = D[at]
+        block = torch.minimum(block, block.T).contiguous()
+        self._data = self._landmark_data = None
+        self._D = D[self.placed.to(device)]
+        self._W = torch.isfinite(self._D).to(torch.float32) if missing else None
+        del D, joined
+        self.landmark_problem = DenseMDE(distance_matrix=block, embedding_dim=embedding_dim, loss=loss,
+                                         constraint=constraints.Centered(), device=device,
+                                         weights=torch.isfinite(block).to(torch.float32) if missing else weights,
+                                         init=init)
+        self.device = self.landmark_problem.device
+        self.placement = None
+        self.X = None
+        self.value = None
+        self.solve_stats = None
+        return self
+
     def _placement(self, X_l):
+        start = "triangulation" if self.init == "classical" else "neighbors"
+        if self._data is None:   # from_graph: the rows of the shortest-path lengths
+            return DensePlacement.weighted(None, X_l, None, distance_matrix=self._D, loss=self.loss,
+                                           device=self.device, weights=self.weights if self._W is None else self._W,
+                                           init=start)
         return DensePlacement.weighted(self._landmark_data, X_l, _take_rows(self._data, self.placed), loss=self.loss,
                                        metric=self.metric, device=self.device, weights=self.weights,
                                        init="triangulation" if self.init == "classical" else "neighbors")

@@ -6,6 +6,8 @@ for what the recipes need: unique undirected edges ``i < j`` with one positive v
 have their values summed).  It lives on the GPU; its adjacency is the symmetrised CSR of an
 ``EdgePlan``.  ``shortest_paths`` [ref: graph.py:345-474] runs batched Bellman-Ford / BFS sweeps
 (``csrc/mde_graph.hip``) instead of one scipy Dijkstra or Cython BFS per node in a process pool.
+``distances_from`` (``csrc/mde_graph_sssp.hip``) solves from a chosen list of nodes and returns one
+row per node: what landmark MDS on a graph (``LandmarkMDE.from_graph``) and Isomap read.
 """
 import ctypes
 import math
@@ -161,6 +163,70 @@ def shortest_paths(graph, retain_fraction=1.0, max_length=None, seed=0, verbose=
             ctypes.byref(count), _lib.stream_ptr(device)))
     m = count.value
     return Graph._from_unique_edges(edges[:m], dist[:m], n)
+
+
+def _check_sources(sources, n):
+    """``sources`` (an int sequence, a numpy array or a torch tensor of node indices) as a contiguous int64 tensor
+    on whatever device it came on; ``ValueError`` when it is empty, not integral, or names a node outside [0, n)."""
+    if isinstance(sources, torch.Tensor):
+        src = sources.detach()
+    else:
+        import numpy as np
+        src = torch.as_tensor(np.asarray(sources))
+    if src.numel() < 1:
+        raise ValueError("`sources` is empty: at least one source node is needed")
+    if src.dtype in (torch.bool,) or src.is_floating_point() or src.is_complex():
+        raise ValueError(f"`sources` must hold node indices (integers), got dtype {src.dtype}")
+    src = src.reshape(-1).to(torch.int64).contiguous()
+    lo, hi = int(src.min()), int(src.max())
+    if lo < 0 or hi >= n:
+        raise ValueError(f"`sources` must lie in [0, n) = [0, {n}); it holds {lo if lo < 0 else hi}")
+    return src
+
+
+def distances_from(graph, sources, max_length=None):
+    """Shortest-path lengths from the nodes ``sources`` to every node: a float32 ``[n, m]`` tensor on the GPU, one
+    row per node; column ``b`` holds the lengths from ``sources[b]`` (0 at the source itself, ``inf`` where no path
+    exists or none of length ``<= max_length``).  ``sources``: an int sequence, a numpy array or a torch tensor of
+    node indices, in any order, repeats allowed.  ``csrc/mde_graph_sssp.hip``: the result has the
+    same bits on every run, and the bits ``shortest_paths`` reports for the pair.  ``ValueError`` for a non-``Graph``,
+    an empty list, a source outside ``[0, n)`` and negative or non-finite edge lengths."""
+    if not isinstance(graph, Graph):
+        raise ValueError("`graph` must be a pymde_amd.Graph instance.")
+    src = _check_sources(sources, graph.n_items)
+    plan, w = _path_lengths(graph)
+    return _distances_from(plan, w, src, max_length)
+
+
+def _path_lengths(graph):
+    """``(plan, w)`` as ``mde_graph_distances_from`` takes them: the graph's plan and its edge lengths in plan order
+    (``None`` for unit lengths), checked to be finite and non-negative with one reduction."""
+    lengths = graph.distances
+    if lengths.numel() and not bool((torch.isfinite(lengths) & (lengths >= 0)).all()):
+        raise ValueError("the edge lengths of `graph` must be finite and non-negative for shortest paths")
+    plan = graph.plan()
+    return plan, (None if bool((lengths == 1.0).all()) else plan.expand(lengths, 0))
+
+
+def _distances_from(plan, w, src, max_length=None):
+    """The call itself: ``src`` a checked int64 tensor, ``(plan, w)`` from ``_path_lengths``."""
+    lib = _lib.load()
+    device, n, m = plan.device, int(plan.n), int(src.numel())
+    src = src.to(device)
+    out = torch.empty((n, m), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.mde_graph_distances_from(plan.handle, _lib.ptr(w),
+                                                float(max_length) if max_length is not None else 0.0, m,
+                                                _lib.ptr(src), _lib.ptr(out), _lib.stream_ptr(device)))
+    return out
+
+
+def last_distances_stats():
+    """What the last ``distances_from`` of this thread did, as a dict: ``sweeps``, ``tiles_relaxed`` (a tile is a
+    node and 64 consecutive source columns), ``tiles_per_sweep`` and ``heavy_nodes``."""
+    stats = (ctypes.c_int64 * 4)()
+    _lib.check(_lib.load().mde_graph_distances_stats(stats))
+    return dict(zip(("sweeps", "tiles_relaxed", "tiles_per_sweep", "heavy_nodes"), (int(v) for v in stats)))
 
 
 def k_nearest_neighbors(graph, k, graph_distances=False, max_distance=None, verbose=False):

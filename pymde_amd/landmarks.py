@@ -8,6 +8,9 @@ probability proportional to its squared distance to them, which is less drawn to
 pass over the data per landmark, and how well ``m`` landmarks cover the data is the covering radius: the largest
 distance from a row to its nearest landmark (``LandmarkSelection.distance.max()``).
 
+``select_graph`` is farthest-point selection among the nodes of a ``Graph`` under its shortest-path metric (one
+``graph.distances_from`` solve per landmark).
+
 ``LandmarkMDE(..., selection=...)`` and ``preserve_distances(..., landmarks=m, landmark_selection=...)`` use it.
 """
 import collections
@@ -15,6 +18,7 @@ import collections
 import torch
 
 from pymde_amd import _lib, util
+from pymde_amd import graph as _graph
 from pymde_amd import metrics as _metrics
 from pymde_amd import preprocess as _preprocess
 from pymde_amd import quality as _quality
@@ -139,3 +143,59 @@ def select(data, m, method="farthest", metric="euclidean", start=None, seed=None
     else:
         radius, distance = radius2.mul_(0.5), mind2.mul_(0.5)
     return LandmarkSelection(idx.to(torch.int64), radius, nearest.to(torch.int64), distance)
+
+
+def _check_count(m, n, what="m"):
+    if isinstance(m, bool) or int(m) != m:
+        raise ValueError(f"`{what}` must be a number of nodes (an int), got {m!r}")
+    m = int(m)
+    if not 1 <= m <= n:
+        raise ValueError(f"`{what}` must lie in [1, n] = [1, {n}], got {m}")
+    return m
+
+
+def select_graph(graph, m, start=None, seed=None, max_length=None):
+    """``m`` distinct nodes of a ``Graph`` chosen by farthest-point selection under its shortest-path metric: the
+    ``LandmarkSelection(indices, radius, nearest, distance)`` of ``select``, with path lengths for distances.
+
+    Every step is one single-source ``graph.distances_from`` solve from the node just chosen, a running minimum and
+    an arg-max; ties go to the smallest node index.  A node no landmark reaches (none within ``max_length``, if given)
+    is at distance ``inf`` and is therefore taken next: every component of the graph gets a landmark before any gets
+    a second one, and ``radius`` is ``inf`` at those positions (and at position 0).  ``start`` and ``seed`` as in
+    ``select``.  k-means++ has no graph form here."""
+    if not isinstance(graph, _graph.Graph):
+        raise ValueError("`graph` must be a pymde_amd.Graph instance; the rows of a data matrix go to `select`")
+    n = int(graph.n_items)
+    m = _check_count(m, n)
+    if start is not None:
+        if isinstance(start, bool) or int(start) != start:
+            raise ValueError(f"`start` must be a node index (an int), got {start!r}")
+        start = int(start)
+        if not 0 <= start < n:
+            raise ValueError(f"`start` must lie in [0, n) = [0, {n}), got {start}")
+    if seed is None:
+        seed = int(util.np_rng().integers(0, 2 ** 63 - 1))
+    if start is None:
+        start = int(_quality._sample_rows(n, 1, int(seed))[0])
+    plan, w = _graph._path_lengths(graph)
+    device = plan.device
+    inf = float("inf")
+    order = torch.arange(n, dtype=torch.int64, device=device)
+    distance = torch.full((n,), inf, dtype=torch.float32, device=device)
+    nearest = torch.zeros(n, dtype=torch.int64, device=device)
+    chosen = torch.zeros(n, dtype=torch.bool, device=device)
+    indices = torch.empty(m, dtype=torch.int64, device=device)
+    radius = torch.empty(m, dtype=torch.float32, device=device)
+    node = torch.tensor([start], dtype=torch.int64, device=device)
+    for t in range(m):
+        indices[t] = node[0]
+        radius[t] = distance[node[0]]
+        chosen[node[0]] = True
+        d = _graph._distances_from(plan, w, node, max_length).reshape(-1)
+        closer = d < distance                     # (strict: ties stay with the earlier landmark)
+        nearest[closer] = t
+        distance = torch.minimum(distance, d)
+        # the farthest node not chosen yet; among equals the smallest index, whatever argmax would return
+        score = torch.where(chosen, torch.full_like(distance, -1.0), distance)
+        node = torch.where(score == score.max(), order, n).min().reshape(1)
+    return LandmarkSelection(indices, radius, nearest, distance)

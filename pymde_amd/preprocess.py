@@ -254,6 +254,35 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
 
 
+def neighbor_graph(data, k, *, metric="euclidean", max_distance=None, **search):
+    """The k-nearest-neighbour graph of the rows of a data matrix as a ``Graph`` whose edge values are LENGTHS: the
+    union of the directed neighbour lists of ``_neighbor_lists`` (``search``: every keyword of that search --
+    ``device``, ``approximate``, ``n_lists``, ``n_probe``, ``seed``, ``verbose``, ``precision``, ``n_candidates``,
+    ``n_refine``), each edge with the metric's distance of its two rows; an edge listed from both ends takes the
+    smaller of the two values (they are the same pair computed twice and can differ in the last bits).  What
+    ``graph.distances_from`` and ``LandmarkMDE.from_graph`` walk for Isomap."""
+    if _is_graph(data):
+        raise ValueError("neighbor_graph takes a data matrix; a Graph is already a graph")
+    from pymde_amd import graph as _graph
+    idx, values, bound, root, scale = _neighbor_lists(data, k, max_distance=max_distance, metric=metric, **search)
+    n, device = int(idx.shape[0]), idx.device
+    i = torch.arange(n, dtype=torch.int64, device=device).unsqueeze(1).expand_as(idx).reshape(-1)
+    j = idx.reshape(-1).to(torch.int64)
+    values = values.reshape(-1)
+    keep = (j >= 0) & (j != i)
+    if bound is not None:
+        keep &= values <= bound
+    i, j, values = i[keep], j[keep], values[keep]
+    lengths = (values.clamp_min(0.0).sqrt() if root else values) * scale
+    key = torch.minimum(i, j) * n + torch.maximum(i, j)
+    uniq, inverse = torch.unique(key, sorted=True, return_inverse=True)
+    # (Graph.from_edges would SUM the two listings of a mutual pair)
+    shortest = torch.full((uniq.shape[0],), float("inf"), dtype=torch.float32, device=device)
+    shortest.scatter_reduce_(0, inverse, lengths.to(torch.float32), reduce="amin")
+    edges = torch.stack([uniq // n, uniq % n], dim=1).contiguous()
+    return _graph.Graph._from_unique_edges(edges, shortest, n)
+
+
 def _neighbor_lists(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,
                     n_lists=None, n_probe=None, seed=0, verbose=False, metric="euclidean",
                     precision="float32", n_candidates=None, n_refine=0):

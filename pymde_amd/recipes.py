@@ -237,6 +237,46 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
                        device=edges.device)
 
 
+def preserve_geodesics(data, embedding_dim=2, n_neighbors=15, landmarks=None, *, loss=losses.Quadratic,
+                       landmark_selection="farthest", init=None, metric="euclidean", seed=None, device=None,
+                       verbose=False, **search):
+    """Preserve the geodesic distances of the data: landmark MDS under the shortest-path metric of a neighbour graph
+    (Landmark Isomap, de Silva and Tenenbaum); returns the ``dense.LandmarkMDE`` of ``LandmarkMDE.from_graph``.
+
+    ``data``: a data matrix, whose ``preprocess.neighbor_graph(data, n_neighbors, metric=metric, **search)`` is used
+    (``search``: the keywords of the k-NN search), or a ``Graph``, used as it is with its values as edge lengths.
+    ``landmarks``: how many (``None``: ``min(1000, n // 2)``), chosen by ``landmark_selection`` (``"farthest"``, the
+    default, or ``"uniform"``).  ``init``: ``"random"``, ``"classical"``, or ``None``: classical when every (node,
+    landmark) pair is joined by a path, random otherwise (one logged line says why).  The cost is one shortest-path
+    solve from the landmarks, O(n m) memory; a graph of several components is embedded with the pairs across
+    components left out, so their relative position is arbitrary."""
+    if init is not None:
+        _dense.check_init(init)
+    landmark_selection = _landmarks.resolve_selection(landmark_selection)
+    if landmark_selection == _landmarks.KMEANSPP:
+        raise ValueError("landmark_selection='kmeans++' has no graph form; the selections here are 'farthest' and "
+                         "'uniform'")
+    if isinstance(data, _graph.Graph):
+        _metrics.check_graph(_metrics.resolve(metric))
+        graph = data
+    else:
+        if not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
+            raise ValueError("`data` must be a np.ndarray/torch.Tensor/sparse data matrix, or a pymde_amd.Graph.")
+        n_items = int(data.shape[0])
+        if landmarks is not None:
+            _dense.check_landmarks(landmarks, n_items, None)
+        if verbose:
+            problem.LOGGER.info(f"Building the {n_neighbors}-nearest-neighbour graph of {n_items} rows")
+        graph = preprocess.neighbor_graph(data, n_neighbors, metric=metric, device=device, verbose=verbose, **search)
+    if landmarks is None:
+        landmarks = min(1000, graph.n_items // 2)
+    if verbose:
+        problem.LOGGER.info(f"Shortest paths from {landmarks} landmarks ({landmark_selection}) to "
+                            f"{graph.n_items} nodes")
+    return _dense.LandmarkMDE._build_from_graph(graph, landmarks, embedding_dim, loss, None, seed,
+                                                landmark_selection, init, None, None)
+
+
 def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights=None,
                               init="random"):
     """``preserve_distances(dense=True)``: the ``DenseMDE`` over every pair of the rows of ``data``."""
