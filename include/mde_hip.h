@@ -398,6 +398,44 @@ int mde_pair_moments(int64_t n, int32_t nfa, const float* A, int32_t mode_a, int
 int mde_pair_histogram(int64_t n, int32_t nfa, const float* A, int32_t mode_a, int32_t nfb, const float* B,
                        int32_t mode_b, int64_t n_q, const int32_t* q_rows, int32_t slices, int32_t bins, float a_lo,
                        float a_hi, float b_lo, float b_hi, int64_t* counts, void* work, void* stream);
+/* An embedding scored against a matrix of dissimilarities (csrc/mde_matrix_quality.hip): what the
+ * matrix_* and graph_* functions of pymde_amd.quality are computed from, where D is read, not formed from data rows.
+ * Dm [n, m] (float32, row-major, on the device; element offsets are 64-bit, n m may exceed 2^31) is the layout that
+ * mde_graph_distances_from writes: row i is item i, column b holds the dissimilarity to item items[b].  items int32
+ * [m] on the device may repeat and come in any order (an entry outside [0, n) is the caller's error and is not
+ * checked); NULL: items[b] = b, and m == n.  X [n, d] (float32, row-major; 1 <= d <= 8) is the embedding.
+ * A pair (i, b) does not count when items[b] == i (the item itself) or when Dm[i][b] is not finite or equals FLT_MAX
+ * (a missing pair, the convention of mde_pair_loss; a NaN is skipped the same way and is the caller's error).  For a
+ * counted pair D = Dm[i][b] and E = |x_i - x_items[b]|, sqrtf of the fmaf chain over the d differences as in
+ * mde_pair_loss.
+ * mde_matrix_moments: row_sums double [n, 5] = the sums over the row's counted pairs of D, E, D^2, E^2, D E
+ * (accumulated in double, the products formed in double from the float32 D and E); row_count int64 [n] = the number
+ * of counted pairs of the row; row_max float [n, 2] = the row's largest D and E (0 without a counted pair); totals
+ * double [8] = the five sums over all rows, the largest D, the largest E, the total count: the layout of
+ * mde_pair_moments.  No floating-point atomics and a fixed order: the same bits on every run; a row's sums depend
+ * on n, m and the inputs only, never on the grid; totals come from two further launches that add the rows in
+ * blocks of 4096 rows, then the blocks, both in index order.
+ * mde_matrix_histogram: the same walk and the same rule; every counted pair with d_lo <= D <= d_hi and e_lo <= E <=
+ * e_hi adds one to counts[bd][be], binned as in mde_pair_histogram (the last bin closed); counts int64 [bins, bins]
+ * on the device is added to, so the caller zeroes it.  1 <= bins <= 64.  Integer atomics only.
+ * work: mde_matrix_moments_work_bytes(n, m) bytes of scratch for mde_matrix_moments (the partial totals); the
+ * histogram needs none; the calls allocate nothing.  1 <= n < 2^31, 1 <= m < 2^31.  Arguments are checked on the host
+ * before any launch: MDE_E_INVALID with a message.  ASYNC. */
+int64_t mde_matrix_moments_work_bytes(int64_t n, int64_t m);
+int mde_matrix_moments(int64_t n, int64_t m, const float* Dm, const int32_t* items, int32_t d, const float* X,
+                       double* row_sums, int64_t* row_count, float* row_max, double* totals, void* work,
+                       void* stream);
+int mde_matrix_histogram(int64_t n, int64_t m, const float* Dm, const int32_t* items, int32_t d, const float* X,
+                         int32_t bins, float d_lo, float d_hi, float e_lo, float e_hi, int64_t* counts, void* stream);
+/* Ranks within the columns of Dm (same layout): idx int32 [m, k] (1 <= k <= 64) lists items for every column, and
+ * ranks[b][c] (int32 [m, k]) = the number of items j != items[b] with (Dm[j][b], j) < (Dm[l][b], l), l = idx[b][c],
+ * in lexicographic order: 0-based, ties to the smaller index, the rule of mde_knn_ranks.  +inf is an ordinary value
+ * that sorts last (unreachable items rank after all reachable ones, by index); a NaN is the caller's error.  An
+ * entry that is negative, >= n or the column's own item gets -1 (the entries live on the device; no row is read for
+ * them).  Two launches; integer arithmetic and integer atomics only: the ranks are the same for every grid and on
+ * every run.  No scratch, no allocation.  Arguments are checked on the host before any launch.  ASYNC. */
+int mde_matrix_ranks(int64_t n, int64_t m, const float* Dm, const int32_t* items, int32_t k, const int32_t* idx,
+                     int32_t* ranks, void* stream);
 /* The loss and gradient of a dense MDE problem (csrc/mde_pair_loss.hip): a loss over all
  * P = n (n - 1) / 2 pairs of n items without an edge list, what pymde_amd.DenseMDE minimises.
  * X [n, d] (float32, row-major, on the device; 1 <= d <= 8) is the embedding.  The original deviation D(i, j) of a

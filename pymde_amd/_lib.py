@@ -96,6 +96,11 @@ SYMBOLS = {
                                  c_vp, c_vp]),
     "mde_pair_histogram": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_i32, c_i32, c_f32,
                                    c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "mde_matrix_moments_work_bytes": (c_i64, [c_i64, c_i64]),
+    "mde_matrix_moments": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_matrix_histogram": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp,
+                                     c_vp]),
+    "mde_matrix_ranks": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mde_pair_loss_work_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "mde_pair_loss": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_f32, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_i32,
                               c_vp, c_vp, c_vp, c_vp, c_vp]),

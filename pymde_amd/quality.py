@@ -13,6 +13,11 @@ end of this module tell: Kruskal's ``stress``, the ``distance_correlation`` of a
 ``shepard_histogram``, all functions of sums over every pair that one more pass of the same Gram tile forms in
 O(n) memory (``pair_moments``, ``csrc/mde_pair_moments.hip``).
 
+All of those form the data-side distance from data rows.  Where it exists only as a matrix -- the shortest-path lengths
+of a ``Graph``, which an Isomap embedding is to be judged by, or a caller's precomputed dissimilarities -- the
+``matrix_*`` and ``graph_*`` functions at the end of this module give the same scores from walks of that matrix
+(``csrc/mde_matrix_quality.hip``).
+
 A rank is 0-based and ties go to the smaller index: ``rank(i, j)`` is the number of rows ``l`` (other than
 ``i`` in a self-join) with ``(d2(i, l), l) < (d2(i, j), j)``, where ``d2`` is the float32 squared distance of
 the Euclidean k-NN kernels, bit for bit.  The ranks of a search's own lists are therefore ``0 .. k - 1``.
@@ -488,3 +493,390 @@ def shepard_histogram(data, X, bins=64, range=None, metric="euclidean", sample=N
     counts = _pair_histogram(A, B, bins, range_[0], range_[1], *modes, q_rows=q_rows)
     d_edges, e_edges = (np.linspace(lo, hi, bins + 1, dtype=np.float64) for lo, hi in range_)
     return counts, d_edges, e_edges, int(counts.sum().item())
+
+
+# ---------------------------------------------------------------- scores against a matrix of dissimilarities or a Graph
+# (csrc/mde_matrix_quality.hip)
+MAX_EMBEDDING_DIM = 8  # MQ_MAX_D of csrc/mde_matrix_quality.hip: the limit of the dense problems
+_BATCH_ELEMENTS = 2 ** 29   # a batch of graph_* sources holds at most this many float32 path lengths (2 GiB)
+
+MatrixMoments = collections.namedtuple(
+    "MatrixMoments", PairMoments._fields + ("row_counts", "missing"))
+MatrixMoments.__doc__ = """A ``PairMoments`` over the counted pairs (i, b) of a dissimilarity matrix [n, m] -- ``row_sums``
+float64 [n, 5] holds every item's own sums over its counted columns, ``rows`` is None -- with ``row_counts`` int64 [n]
+on the GPU, the number of counted pairs of every item, and ``missing``, the number of pairs skipped because their
+entry is ``inf`` or ``FLT_MAX`` (the ``m`` pairs of an item with itself are neither counted nor missing)."""
+
+
+def _check_items(items, n, m):
+    """``items`` as a contiguous int32 tensor (on the device it came on), or None: ``ValueError`` unless it is a
+    vector of ``m`` whole numbers in [0, n)."""
+    if items is None:
+        if m != n:
+            raise ValueError(f"`distances` is [{n}, {m}]: without `items` its columns are the items themselves and "
+                             "it must be square")
+        return None
+    t = items.detach() if isinstance(items, torch.Tensor) else torch.as_tensor(np.asarray(items))
+    if t.dim() != 1 or int(t.numel()) != m:
+        raise ValueError(f"`items` must be a vector with one entry per column of `distances` ({m}), got shape "
+                         f"{tuple(t.shape)}")
+    if t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
+        raise ValueError(f"`items` must hold item indices (integers), got dtype {t.dtype}")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= n:
+        raise ValueError(f"`items` must lie in [0, n) = [0, {n}); it holds {lo if lo < 0 else hi}")
+    return t.to(torch.int32).contiguous()
+
+
+def _check_embedding(X, n):
+    _check_matrix(X, "X")
+    if int(X.shape[0]) != n:
+        raise ValueError(f"the distances have {n} rows and the embedding `X` has {int(X.shape[0])}; they must agree")
+    d = int(X.shape[1])
+    if not 1 <= d <= MAX_EMBEDDING_DIM:
+        raise ValueError(f"the embedding `X` has {d} columns; the matrix scores take 1 to {MAX_EMBEDDING_DIM}")
+    return d
+
+
+def _check_distances(distances, X, items):
+    """The argument checks of the matrix-level scores, before any device is required: (n, m, items)."""
+    if _preprocess._is_graph(distances):
+        raise ValueError("`distances` must be a matrix [n, m]; score a Graph with the graph_* functions")
+    if not hasattr(distances, "shape") or len(distances.shape) != 2:
+        raise ValueError("`distances` must be a matrix [n, m]")
+    n, m = int(distances.shape[0]), int(distances.shape[1])
+    if n < 1 or m < 1:
+        raise ValueError("`distances` needs at least one row and one column")
+    if X is not None:
+        _check_embedding(X, n)
+    return n, m, _check_items(items, n, m)
+
+
+def _device_distances(distances, device):
+    """``distances`` as float32 on ``device``, checked with one reduction to hold no NaN and no negative entry."""
+    Dm = torch.as_tensor(distances).to(device=device, dtype=torch.float32).contiguous()
+    if not bool((Dm >= 0).all()):
+        raise ValueError("`distances` must not hold NaN or negative entries (inf marks a missing pair)")
+    return Dm
+
+
+def _device_embedding(X, device):
+    return torch.as_tensor(X).detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _matrix_moments(Dm, X, items):
+    """``mde_matrix_moments`` on prepared tensors of one GPU: (row_sums, row_count, row_max, totals) on that GPU."""
+    n, m, device = int(Dm.shape[0]), int(Dm.shape[1]), Dm.device
+    lib = _lib.load()
+    row_sums = torch.empty((n, 5), dtype=torch.float64, device=device)
+    row_count = torch.empty(n, dtype=torch.int64, device=device)
+    row_max = torch.empty((n, 2), dtype=torch.float32, device=device)
+    totals = torch.empty(8, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        work = _lib.work_buffer(lib.mde_matrix_moments_work_bytes, n, m, device=device)
+        _lib.check(lib.mde_matrix_moments(n, m, _lib.ptr(Dm), _lib.ptr(items), int(X.shape[1]), _lib.ptr(X),
+                                          _lib.ptr(row_sums), _lib.ptr(row_count), _lib.ptr(row_max),
+                                          _lib.ptr(totals), _lib.ptr(work), _lib.stream_ptr(device)))
+    return row_sums, row_count, row_max, totals
+
+
+def _matrix_histogram(Dm, X, items, bins, d_range, e_range, counts):
+    """``mde_matrix_histogram``: adds to ``counts`` int64 [bins, bins] on the GPU of the tensors."""
+    device = Dm.device
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().mde_matrix_histogram(int(Dm.shape[0]), int(Dm.shape[1]), _lib.ptr(Dm), _lib.ptr(items),
+                                                    int(X.shape[1]), _lib.ptr(X), bins, d_range[0], d_range[1],
+                                                    e_range[0], e_range[1], _lib.ptr(counts),
+                                                    _lib.stream_ptr(device)))
+    return counts
+
+
+def _moments_from_parts(n_pairs, row_sums, row_count, totals):
+    """A ``MatrixMoments`` from ``totals`` (a list of 8 floats) and the row outputs; ``n_pairs`` pairs were walked,
+    the item itself excluded."""
+    count = int(round(totals[7]))
+    return MatrixMoments(count, totals[0], totals[1], totals[2], totals[3], totals[4], totals[5], totals[6], row_sums,
+                         None, row_count, n_pairs - count)
+
+
+def _prepared_matrix(distances, X, items):
+    n, m, items = _check_distances(distances, X, items)
+    device = _device_of(*(a for a in (distances, X) if isinstance(a, torch.Tensor)))
+    Dm = _device_distances(distances, device)
+    return Dm, _device_embedding(X, device) if X is not None else None, (None if items is None else items.to(device))
+
+
+def matrix_moments(distances, X, items=None):
+    """The sums the matrix scores are functions of, for any precomputed dissimilarities (sklearn's
+    ``metric="precomputed"``): a ``MatrixMoments``.
+
+    ``distances`` [n, m] (a torch or numpy array, copied to the GPU as float32): row ``i`` is item ``i`` and column
+    ``b`` holds the dissimilarity D to item ``items[b]`` -- the layout of ``graph.distances_from``.  ``items``: ``m``
+    item indices, repeats and any order allowed; ``None``: a square matrix, column ``b`` is item ``b``.  ``X`` [n, d],
+    ``1 <= d <= 8``: the embedding; E is the float32 Euclidean distance formed from the differences.  The pair of an
+    item with itself is not counted; an entry that is ``inf`` (or FLT_MAX) is a missing pair, skipped and reported in
+    ``missing``.  NaN and negative entries are a ``ValueError`` (one reduction on the GPU).  Sums in float64 in a
+    fixed order: the same bits on every run."""
+    Dm, X, items = _prepared_matrix(distances, X, items)
+    row_sums, row_count, _, totals = _matrix_moments(Dm, X, items)
+    n, m = int(Dm.shape[0]), int(Dm.shape[1])
+    return _moments_from_parts(n * m - m, row_sums, row_count, totals.cpu().tolist())
+
+
+def _stress_from(moments, scale, per_item):
+    scores = _scores_from_moments(moments, scale, per_item)
+    return (scores.stress, scores.per_item) if per_item else scores.stress
+
+
+def matrix_stress(distances, X, items=None, scale="optimal", per_item=False):
+    """Kruskal's stress-1 of the embedding ``X`` against the dissimilarities ``distances`` over the counted pairs:
+    ``stress`` with D read from a matrix.  ``distances``, ``X``, ``items`` as in ``matrix_moments``; ``scale`` as in
+    ``stress``.  ``per_item=True`` returns ``(stress, per_row)``: float32 [n] on the GPU, one value per item over its
+    counted columns under the same ``alpha``; an item without a counted pair (or whose D are all zero) is NaN."""
+    _check_scale(scale)
+    return _stress_from(matrix_moments(distances, X, items), scale, per_item)
+
+
+def matrix_correlation(distances, X, items=None):
+    """Pearson's correlation of D and E over the counted pairs of a dissimilarity matrix: ``distance_correlation``
+    with D read from a matrix (not Szekely's dCor).  Arguments as in ``matrix_moments``; a Python float."""
+    return _scores_from_moments(matrix_moments(distances, X, items)).correlation
+
+
+def _range_from_maxima(top):
+    return tuple((0.0, v if v > 0.0 else 1.0) for v in top)      # a space whose distances are all zero: one unit
+
+
+def matrix_shepard_histogram(distances, X, items=None, bins=64, range=None):
+    """``shepard_histogram`` with D read from a matrix: ``(counts, d_edges, e_edges, n_counted)``.  ``range=None``
+    takes ``[0, max D] x [0, max E]`` over the counted pairs from a moments pass first.  Other arguments as in
+    ``matrix_moments``; missing pairs are not counted."""
+    bins, range_ = _check_bins(bins), _check_range(range)
+    Dm, X, items = _prepared_matrix(distances, X, items)
+    if range_ is None:
+        range_ = _range_from_maxima(_matrix_moments(Dm, X, items)[3][5:7].cpu().tolist())
+    counts = torch.zeros((bins, bins), dtype=torch.int64, device=Dm.device)
+    _matrix_histogram(Dm, X, items, bins, range_[0], range_[1], counts)
+    d_edges, e_edges = (np.linspace(lo, hi, bins + 1, dtype=np.float64) for lo, hi in range_)
+    return counts, d_edges, e_edges, int(counts.sum().item())
+
+
+def _check_lists(idx, m):
+    _check_matrix(idx, "idx")
+    if int(idx.shape[0]) != m:
+        raise ValueError(f"`idx` has {int(idx.shape[0])} rows for {m} columns of `distances`")
+    k = int(idx.shape[1])
+    if not 1 <= k <= MAX_LIST:
+        raise ValueError(f"`idx` lists {k} items per column; the rank kernel takes 1 to {MAX_LIST}")
+    return k
+
+
+def _matrix_ranks(Dm, idx, items):
+    """``mde_matrix_ranks`` on prepared tensors of one GPU: int32 [m, k]."""
+    device = Dm.device
+    ranks = torch.empty(tuple(idx.shape), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().mde_matrix_ranks(int(Dm.shape[0]), int(Dm.shape[1]), _lib.ptr(Dm), _lib.ptr(items),
+                                                int(idx.shape[1]), _lib.ptr(idx), _lib.ptr(ranks),
+                                                _lib.stream_ptr(device)))
+    return ranks
+
+
+def matrix_ranks(distances, idx, items=None):
+    """The rank, within its column of ``distances`` [n, m], of every listed item: int32 [m, k] on the GPU.
+
+    ``idx`` [m, k] (``1 <= k <= 64``) lists items for every column; ``ranks[b, c]`` is the number of items ``j``
+    other than ``items[b]`` that precede ``l = idx[b, c]`` in the order ``(distances[j, b], j)``: 0-based, ties to
+    the smaller index, the rule of ``neighbor_ranks``.  ``inf`` is an ordinary value that sorts last: unreachable
+    items rank after all reachable ones, by index.  Entries that are negative, ``>= n`` or the column's own item
+    come back as -1.  ``distances`` and ``items`` as in ``matrix_moments``."""
+    n, m, items = _check_distances(distances, None, items)
+    _check_lists(idx, m)
+    device = _device_of(*(a for a in (distances, idx) if isinstance(a, torch.Tensor)))
+    Dm = _device_distances(distances, device)
+    idx = torch.as_tensor(idx).to(device=device, dtype=torch.int32).contiguous()
+    return _matrix_ranks(Dm, idx, None if items is None else items.to(device))
+
+
+def _sampled_score(ranks, n, k, per_item=False):
+    """``_score_from_ranks`` with the mean taken over the ``m`` listed items, the rows of ``ranks`` [m, k], of ``n``:
+    ``1 - 2 / (m k (2 n - 3 k - 1)) * sum max(0, rank + 1 - k)``; sklearn's value when every item is listed once."""
+    n, k, m = int(n), int(k), int(ranks.shape[0])
+    _check_k(k, n)
+    penalty = (ranks.to(torch.int64) + (1 - k)).clamp_(min=0).sum(dim=1)
+    scale = 2.0 / (m * k * (2.0 * n - 3.0 * k - 1.0))
+    score = 1.0 - int(penalty.sum().item()) * scale
+    if not per_item:
+        return score
+    return score, (1.0 - penalty.to(torch.float64) * (scale * m)).to(torch.float32)
+
+
+def _embedding_lists(X, k, items):
+    """The exact float32 k-NN lists of the embedding (its self-join, as ``trustworthiness`` takes them) for the
+    rows ``items`` (int64 on the GPU; None: every row)."""
+    rows = _self_rows(X, _metrics.EUCLIDEAN, X.device, "X")
+    if items is None or k == MAX_LIST or 2 * int(items.numel()) > int(X.shape[0]):
+        idx, _ = _preprocess._dense_knn_lists(rows, k)
+        return idx if items is None else idx[items].contiguous()
+    # A few rows of many: their k + 1 nearest rows by the query-against-corpus search, which orders by the same
+    # (d2, index) with the same bits, and the row itself taken out.  The first k of the others among the k + 1
+    # nearest are the k nearest of the others whether or not the row itself is among them: the self-join's lists.
+    idx, _ = _preprocess._cross_knn_lists(rows[items].contiguous(), rows, k + 1)
+    others = idx != items.to(torch.int32)[:, None]
+    keep = torch.argsort((~others).to(torch.int8), dim=1, stable=True)[:, :k]
+    return torch.gather(idx, 1, keep).contiguous()
+
+
+def matrix_trustworthiness(distances, X, n_neighbors=5, items=None, per_item=False):
+    """``trustworthiness`` against precomputed dissimilarities: the exact ``n_neighbors`` nearest neighbours in the
+    embedding ``X`` of every item ``items[b]`` are ranked within column ``b`` of ``distances`` (``matrix_ranks``),
+    and the score is ``1 - 2 / (m k (2 n - 3 k - 1)) * sum max(0, rank + 1 - k)``: the mean over the ``m`` listed
+    items, and the value of ``sklearn.manifold.trustworthiness(distances, X, metric="precomputed")`` when ``items``
+    is every item (ties apart: here they go to the smaller index).  ``inf`` entries rank last.  ``X`` may have any
+    number of columns.  ``per_item=True`` returns ``(score, per_column)``, float32 [m] on the GPU."""
+    n, m, items = _check_distances(distances, None, items)
+    _check_matrix(X, "X")
+    if int(X.shape[0]) != n:
+        raise ValueError(f"the distances have {n} rows and the embedding `X` has {int(X.shape[0])}; they must agree")
+    k = _check_k(n_neighbors, n)
+    device = _device_of(*(a for a in (distances, X) if isinstance(a, torch.Tensor)))
+    Dm = _device_distances(distances, device)
+    items = None if items is None else items.to(device)
+    idx = _embedding_lists(_device_embedding(X, device), k, None if items is None else items.to(torch.int64))
+    return _sampled_score(_matrix_ranks(Dm, idx, items), n, k, per_item)
+
+
+# ---- the same against the shortest-path lengths of a Graph, from all nodes or a sample of them
+def _check_graph(graph, X, sample, limit_d=True):
+    """The argument checks of the graph-level scores, before any device is required: (n, m) with ``m`` the number of
+    sampled sources, None for all nodes."""
+    from pymde_amd import graph as _graph
+    if not isinstance(graph, _graph.Graph):
+        raise ValueError("`graph` must be a pymde_amd.Graph instance.")
+    n = int(graph.n_items)
+    if limit_d:
+        _check_embedding(X, n)
+    else:
+        _check_matrix(X, "X")
+        if int(X.shape[0]) != n:
+            raise ValueError(f"`graph` has {n} nodes and the embedding `X` has {int(X.shape[0])} rows; they must agree")
+    if sample is not None:
+        if isinstance(sample, bool) or int(sample) != sample or not 1 <= int(sample) <= n:
+            raise ValueError(f"sample must be None or a whole number of source nodes in [1, {n}], got {sample!r}")
+        sample = int(sample) if int(sample) < n else None
+    return n, sample
+
+
+def _batch_columns(n, batch=None):
+    """The number of sources of one ``distances_from`` call: at most 2 GiB of path lengths, a multiple of 64."""
+    if batch is not None:
+        return int(batch)
+    return max(64, (_BATCH_ELEMENTS // n) // 64 * 64)
+
+
+def _graph_batches(graph, n, m, seed, max_length, batch):
+    """Yields ``(sources int64 on the GPU, Dm [n, len(sources)])`` for the sources of a graph-level score, in order:
+    every node, or the ``m`` nodes of ``_sample_rows(n, m, seed)``."""
+    from pymde_amd import graph as _graph
+    plan, w = _graph._path_lengths(graph)
+    sources = torch.arange(n) if m is None else _sample_rows(n, m, seed)
+    sources = sources.to(plan.device)
+    step = _batch_columns(n, batch)
+    for lo in range(0, int(sources.numel()), step):
+        src = sources[lo:lo + step].contiguous()
+        yield src, _graph._distances_from(plan, w, src, max_length)
+
+
+def graph_moments(graph, X, sample=None, seed=0, max_length=None, _batch=None):
+    """``matrix_moments`` against the shortest-path lengths of ``graph`` (a ``MatrixMoments``): D is the geodesic
+    from a source node to every node (``graph.distances_from``), E the Euclidean distance in the embedding ``X``
+    [n, d], ``1 <= d <= 8`` -- the yardstick of ``preserve_geodesics``, ``DenseMDE.from_graph`` and
+    ``LandmarkMDE.from_graph`` embeddings.  ``sample=None``: every node is a source, all ``n (n - 1)`` ordered pairs;
+    ``sample=m``: the ``m`` nodes ``_sample_rows(n, m, seed)``, the rule of ``pair_moments``' ``sample=``.
+    Pairs without a path (or none of length ``<= max_length``) are missing: skipped, and counted in ``missing``.
+
+    The sources go through ``distances_from`` in batches of at most ``max(64, 2^29 / n rounded down to a multiple of
+    64)`` columns (2 GiB); the batches' float64 row sums and totals are added in batch order, so the result is the
+    same bits on every run (another batch size changes the last bits of the sums that involve E)."""
+    n, m = _check_graph(graph, X, sample)
+    X = _device_embedding(X, graph.plan().device)
+    row_sums = row_count = None
+    totals, n_pairs = [0.0] * 8, 0
+    for src, Dm in _graph_batches(graph, n, m, seed, max_length, _batch):
+        s, c, _, t = _matrix_moments(Dm, X, src.to(torch.int32))
+        t = t.cpu().tolist()
+        if row_sums is None:
+            row_sums, row_count = s, c
+        else:
+            row_sums += s
+            row_count += c
+        totals = [a + b for a, b in zip(totals[:5], t[:5])] + [max(totals[5], t[5]), max(totals[6], t[6]),
+                                                                totals[7] + t[7]]
+        n_pairs += (n - 1) * int(src.numel())
+    return _moments_from_parts(n_pairs, row_sums, row_count, totals)
+
+
+def graph_stress(graph, X, scale="optimal", per_item=False, sample=None, seed=0, max_length=None, _batch=None):
+    """Kruskal's stress-1 of the embedding ``X`` against the shortest-path lengths of ``graph``: what an Isomap
+    embedding is to be judged by (the Euclidean ``stress`` penalises a rolled strip for being unrolled).  ``scale``
+    and ``per_item`` as in ``matrix_stress`` (``per_item``: one value per node over the sources that reach it);
+    other arguments as in ``graph_moments``."""
+    _check_scale(scale)
+    return _stress_from(graph_moments(graph, X, sample, seed, max_length, _batch), scale, per_item)
+
+
+def graph_correlation(graph, X, sample=None, seed=0, max_length=None, _batch=None):
+    """Pearson's correlation of the shortest-path lengths of ``graph`` and the distances in the embedding ``X``
+    over the connected pairs.  Arguments as in ``graph_moments``; a Python float."""
+    return _scores_from_moments(graph_moments(graph, X, sample, seed, max_length, _batch)).correlation
+
+
+def graph_shepard_histogram(graph, X, bins=64, range=None, sample=None, seed=0, max_length=None, _batch=None):
+    """``shepard_histogram`` against the shortest-path lengths of ``graph``: ``(counts, d_edges, e_edges,
+    n_counted)``.  ``range=None`` takes the maxima from a ``graph_moments`` pass first (the paths are solved twice).
+    The counts of the batches add.  Other arguments as in ``graph_moments``."""
+    bins, range_ = _check_bins(bins), _check_range(range)
+    n, m = _check_graph(graph, X, sample)
+    if range_ is None:
+        mom = graph_moments(graph, X, sample, seed, max_length, _batch)
+        range_ = _range_from_maxima((mom.max_d, mom.max_e))
+    X = _device_embedding(X, graph.plan().device)
+    counts = torch.zeros((bins, bins), dtype=torch.int64, device=X.device)
+    for src, Dm in _graph_batches(graph, n, m, seed, max_length, _batch):
+        _matrix_histogram(Dm, X, src.to(torch.int32), bins, range_[0], range_[1], counts)
+    d_edges, e_edges = (np.linspace(lo, hi, bins + 1, dtype=np.float64) for lo, hi in range_)
+    return counts, d_edges, e_edges, int(counts.sum().item())
+
+
+def graph_trustworthiness(graph, X, n_neighbors=5, sample=None, seed=0, per_item=False, _batch=None):
+    """``trustworthiness`` against the shortest-path lengths of ``graph``: the exact ``n_neighbors`` nearest
+    neighbours in the embedding ``X`` of every source node are ranked among the path lengths from that node
+    (``matrix_ranks``); nodes without a path rank last, by index.  The mean is over the sources: every node, or the
+    ``sample`` nodes of ``_sample_rows(n, sample, seed)``.  With every node and no tied path lengths this is
+    ``sklearn.manifold.trustworthiness(D, X, metric="precomputed")`` of the matrix of path lengths.  ``X`` may have
+    any number of columns.  ``per_item=True`` returns ``(score, per_source)``, float32 on the GPU in source order."""
+    n, m = _check_graph(graph, X, sample, limit_d=False)
+    k = _check_k(n_neighbors, n)
+    X = _device_embedding(X, graph.plan().device)
+    ranks = [_matrix_ranks(Dm, _embedding_lists(X, k, None if m is None and int(src.numel()) == n else src),
+                           src.to(torch.int32))
+             for src, Dm in _graph_batches(graph, n, m, seed, None, _batch)]
+    return _sampled_score(torch.cat(ranks), n, k, per_item)
+
+
+def graph_continuity(graph, X, n_neighbors=5, sample=None, seed=0, per_item=False):
+    """``continuity`` against the shortest-path lengths of ``graph``: every node's ``n_neighbors`` nearest nodes
+    under the shortest-path metric (``graph.k_nearest_neighbors(graph_distances=True)``'s lists, ties to the smaller
+    index) are ranked in the embedding ``X``, and the mean is taken over all nodes or the ``sample`` nodes of
+    ``_sample_rows(n, sample, seed)``.  A node that reaches fewer than ``n_neighbors`` others has entries of -1 in
+    its list; they carry no penalty.  Arguments and return value as in ``graph_trustworthiness``."""
+    from pymde_amd import graph as _graph
+    n, m = _check_graph(graph, X, sample, limit_d=False)
+    k = _check_k(n_neighbors, n)
+    device = graph.plan().device
+    idx, _ = _graph._neighbor_lists(graph, k, graph_distances=True)
+    rows = _self_rows(_device_embedding(X, device), _metrics.EUCLIDEAN, device, "X")
+    ranks = _ranks(rows, rows, idx.contiguous(), True)
+    if m is not None:
+        ranks = ranks[_sample_rows(n, m, seed).to(device)]
+    return _sampled_score(ranks, n, k, per_item)
