@@ -324,6 +324,26 @@ int mde_rows_subtract(int64_t n, int32_t nf, const float* data, const double* mu
 int64_t mde_knn_cross_work_bytes(int64_t n_q, int64_t n_c, int32_t k, int32_t slices);
 int mde_knn_cross(int64_t n_q, int64_t n_c, int32_t nf, const float* Q, const float* C, int32_t k,
                   int32_t slices, int32_t* idx_out, float* d2_out, void* work, void* stream);
+/* The nearest pair of rows between every two groups of X [n, nf] (float32, row-major, on the device;
+ * csrc/mde_group_nearest.hip).  labels int32 [n] on the device names the group of every row, a
+ * value of [0, groups); the labels are the caller's contract and are not checked on the host -- a row whose label lies
+ * outside that range belongs to no group and is never read.  2 <= groups <= 1024, 1 <= n < 2^31.
+ * d2_out float32 [groups, groups] and row_out int32 [groups, groups]: for A != B, d2_out[A][B] = d2_out[B][A] is the
+ * smallest squared distance between a row a of group A and a row b of group B, row_out[A][B] is the row of group A
+ * in that pair and row_out[B][A] the row of group B.  With A < B, d2(a, b) is the float32 value mde_knn_cross gives
+ * query a against corpus row b, bit for bit, and the minimum is taken under the key (d2, a, b): ties go to the smaller
+ * a, then the smaller b, so the result is a function of the input alone.  The diagonal, and the row and column of a
+ * group without rows, hold FLT_MAX and -1.
+ * The rows are ordered by label and read through that row map; blocks of at most 64 rows never straddle a label, a
+ * workgroup (query block, slice) forms only the tiles whose candidate label is above its own -- no same-group tile,
+ * no symmetric half -- and keeps one candidate per label; a second kernel folds the blocks and slices in a fixed
+ * order.  No atomics: the same bits on every run and for every slice count (slices as in mde_knn_cross, 0: automatic).
+ * work: mde_group_nearest_work_bytes(n, groups, slices) bytes of scratch (norms, the row map and its sort arrays, the
+ * block table, 12 bytes per (slice, block, group) of partials); the radix sort's own temporary is allocated by the
+ * call.  Arguments are checked on the host before any launch: MDE_E_INVALID with a message.  SYNC. */
+int64_t mde_group_nearest_work_bytes(int64_t n, int32_t groups, int32_t slices);
+int mde_group_nearest(int64_t n, int32_t nf, const float* X, const int32_t* labels, int32_t groups, int32_t slices,
+                      float* d2_out, int32_t* row_out, void* work, void* stream);
 /* The two-stage Euclidean search (csrc/mde_knn_bf16.hip): every pair of a row of Q [n_q, nf]
  * and a row of C [n_c, nf] (float32, row-major, on the device) is ranked by a bf16 Gram product on the bf16
  * matrix cores, every query keeps a shortlist of its n_cand best by (bf16 d2, index), and the shortlist is
@@ -798,6 +818,20 @@ int mde_graph_distances_from(const mde_plan* plan, const float* w, float max_len
 /* What the calling thread's last mde_graph_distances_from did: stats[0] sweeps, [1] tiles (a node x 64 consecutive
  * columns) relaxed over all sweeps, [2] tiles per sweep, [3] nodes handled by the many-wave kernel. */
 int mde_graph_distances_stats(int64_t* stats);
+/* The connected components of the graph of a full (unsharded) plan (csrc/mde_graph_components.hip, DESIGN section
+ * 6u).  labels_out [n] int32 on the device: the label of a node is the rank of its component when the components are
+ * ordered by their smallest node (0 for the component of node 0, and so on: the numbering of
+ * scipy.sparse.csgraph.connected_components); *count_host = the number of components.  Edge values are not read: an
+ * edge of length 0 or inf joins its ends like any other.  Hooking and pointer jumping on one parent array (integer
+ * atomicMin; the fixed point -- every node at the smallest node of its component -- is unique, so the output is the
+ * same on every run): a round is a hook launch (two when some row has more than 64 neighbours: those take a wave
+ * each), a jump launch and a 4-byte read-back; the number of rounds grows with log n, not with the hop diameter.
+ * MDE_E_INVALID (nothing launched) for NULL pointers or a sharded plan, and if 256 rounds do not reach the fixed
+ * point.  Work memory: 12 n bytes.  SYNC. */
+int mde_graph_components(const mde_plan* plan, int32_t* labels_out, int64_t* count_host, void* stream);
+/* What the calling thread's last mde_graph_components did: stats[0] rounds (the last one changed nothing; 0 for a
+ * graph without edges), [1] kernel launches, [2] hook operations that lowered a slot of the parent array. */
+int mde_graph_components_stats(int64_t* stats);
 /* Sample at most num_edges distinct edges i < j uniformly at random from the edges NOT in
  * `exclude` [n_exclude, 2] (NULL / 0: no exclusion); edges_out must hold num_edges rows, sorted by
  * (i, j); *count_host = number written (== num_edges unless the complement is nearly exhausted).

@@ -154,6 +154,10 @@ SYMBOLS = {
                                          c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "mde_graph_distances_from": (c_i32, [c_vp, c_vp, c_f32, c_i64, c_vp, c_vp, c_vp]),
     "mde_graph_distances_stats": (c_i32, [c_vp]),
+    "mde_graph_components": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
+    "mde_graph_components_stats": (c_i32, [c_vp]),
+    "mde_group_nearest_work_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "mde_group_nearest": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mde_sample_edges": (c_i32, [c_i64, c_i64, ctypes.c_uint64, c_vp, c_i64, c_vp,
                                  ctypes.POINTER(c_i64), c_vp]),
     "mde_average_distortion": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(MdeFunc), c_f32, c_vp,

@@ -8,6 +8,8 @@ have their values summed).  It lives on the GPU; its adjacency is the symmetrise
 (``csrc/mde_graph.hip``) instead of one scipy Dijkstra or Cython BFS per node in a process pool.
 ``distances_from`` (``csrc/mde_graph_sssp.hip``) solves from a chosen list of nodes and returns one
 row per node: what landmark MDS on a graph (``LandmarkMDE.from_graph``) and Isomap read.
+``connected_components`` (``csrc/mde_graph_components.hip``) labels the components by hooking and
+pointer jumping; ``preprocess.connect_components`` joins them by bridges between nearest rows.
 """
 import ctypes
 import math
@@ -227,6 +229,34 @@ def last_distances_stats():
     stats = (ctypes.c_int64 * 4)()
     _lib.check(_lib.load().mde_graph_distances_stats(stats))
     return dict(zip(("sweeps", "tiles_relaxed", "tiles_per_sweep", "heavy_nodes"), (int(v) for v in stats)))
+
+
+def connected_components(graph):
+    """The connected components of ``graph``: ``(n_components, labels)``, ``labels`` an int64 ``[n]`` tensor on the
+    GPU.  A node's label is the rank of its component when the components are ordered by their smallest node, the
+    numbering of ``scipy.sparse.csgraph.connected_components``.  Edge values are not read: an edge of length 0 or
+    ``inf`` joins its ends.  A graph without edges has ``n`` components with labels ``0 .. n - 1``.
+    ``csrc/mde_graph_components.hip``: hooking and pointer jumping, a number of rounds that grows
+    with ``log n`` and not with the hop diameter; the same labels on every run.  ``ValueError`` for a non-``Graph``."""
+    if not isinstance(graph, Graph):
+        raise ValueError("`graph` must be a pymde_amd.Graph instance.")
+    plan = graph.plan()
+    device = plan.device
+    labels = torch.empty(graph.n_items, dtype=torch.int32, device=device)
+    count = ctypes.c_int64(0)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().mde_graph_components(plan.handle, _lib.ptr(labels), ctypes.byref(count),
+                                                    _lib.stream_ptr(device)))
+    return int(count.value), labels.to(torch.int64)
+
+
+def last_components_stats():
+    """What the last ``connected_components`` of this thread did, as a dict: ``rounds`` (a hook and a jump launch and
+    one read-back each; the last round changed nothing), ``launches`` and ``hooks`` (hook operations that changed a
+    parent)."""
+    stats = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().mde_graph_components_stats(stats))
+    return dict(zip(("rounds", "launches", "hooks"), (int(v) for v in stats)))
 
 
 def k_nearest_neighbors(graph, k, graph_distances=False, max_distance=None, verbose=False):

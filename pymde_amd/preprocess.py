@@ -9,6 +9,7 @@ Same functions as the reference's ``pymde/preprocess/preprocess.py`` [ref: prepr
     edges here but not the reference's NumPy stream -- parity is distributional (uniform over the
     complement, no duplicates, no excluded edge, requested count).
 """
+import collections
 import ctypes
 import logging
 
@@ -254,15 +255,25 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
 
 
-def neighbor_graph(data, k, *, metric="euclidean", max_distance=None, **search):
+def neighbor_graph(data, k, *, metric="euclidean", max_distance=None, connect=False, **search):
     """The k-nearest-neighbour graph of the rows of a data matrix as a ``Graph`` whose edge values are LENGTHS: the
     union of the directed neighbour lists of ``_neighbor_lists`` (``search``: every keyword of that search --
     ``device``, ``approximate``, ``n_lists``, ``n_probe``, ``seed``, ``verbose``, ``precision``, ``n_candidates``,
     ``n_refine``), each edge with the metric's distance of its two rows; an edge listed from both ends takes the
     smaller of the two values (they are the same pair computed twice and can differ in the last bits).  What
-    ``graph.distances_from`` and ``LandmarkMDE.from_graph`` walk for Isomap."""
+    ``graph.distances_from`` and ``LandmarkMDE.from_graph`` walk for Isomap.
+
+    ``connect`` (default False: nothing changes): ``True`` or ``"pairs"`` joins every two connected components of
+    that graph by their nearest pair of rows, ``"tree"`` joins them by the minimum spanning tree of those pairs
+    (``connect_components``, whose ``Connection.graph`` is returned); not under Manhattan."""
     if _is_graph(data):
         raise ValueError("neighbor_graph takes a data matrix; a Graph is already a graph")
+    if connect:
+        rule = resolve_connect(connect)
+        if _metrics.resolve(metric) == _metrics.MANHATTAN:
+            raise ValueError(_NO_MANHATTAN_WALK)
+        graph = neighbor_graph(data, k, metric=metric, max_distance=max_distance, **search)
+        return connect_components(data, graph, bridges=rule, metric=metric, device=search.get("device")).graph
     from pymde_amd import graph as _graph
     idx, values, bound, root, scale = _neighbor_lists(data, k, max_distance=max_distance, metric=metric, **search)
     n, device = int(idx.shape[0]), idx.device
@@ -281,6 +292,217 @@ def neighbor_graph(data, k, *, metric="euclidean", max_distance=None, **search):
     shortest.scatter_reduce_(0, inverse, lengths.to(torch.float32), reduce="amin")
     edges = torch.stack([uniq // n, uniq % n], dim=1).contiguous()
     return _graph.Graph._from_unique_edges(edges, shortest, n)
+
+
+MAX_GROUPS = 1024        # GN_MAX_GROUPS of csrc/mde_group_nearest.hip: one LDS slot per group
+PAIRS, TREE = "pairs", "tree"
+_NO_MANHATTAN_WALK = ("the nearest pairs between groups have no Manhattan walk (the L1 tile has none); the metrics "
+                      "served are 'euclidean', 'cosine' and 'correlation'")
+
+GroupNearest = collections.namedtuple("GroupNearest", ["groups", "distance", "row"])
+GroupNearest.__doc__ = """The nearest pairs between groups of rows (``nearest_between_groups``): ``groups`` the
+distinct labels in ascending order [g]; ``distance`` float32 [g, g] in the metric's units, ``inf`` on the diagonal;
+``row`` int64 [g, g]: the nearest pair of groups ``A`` and ``B`` is ``(row[A, B], row[B, A])``, -1 on the diagonal."""
+
+Connection = collections.namedtuple("Connection", ["graph", "bridges", "lengths", "labels", "n_components"])
+Connection.__doc__ = """A graph joined into one component (``connect_components``): ``graph`` the old edges with
+their values plus the bridges; ``bridges`` int64 [b, 2] (``i < j``, sorted) and their ``lengths`` float32 [b];
+``labels`` int64 [n] and ``n_components``: the components of the graph that came in."""
+
+
+def resolve_connect(connect):
+    """``"pairs"`` or ``"tree"`` for a ``connect=`` / ``bridges=`` value (``True`` is ``"pairs"``); ``ValueError``
+    for anything else.  Needs no device."""
+    if connect is True:
+        return PAIRS
+    name = connect.strip().lower() if isinstance(connect, str) else connect
+    if not isinstance(name, str) or name not in (PAIRS, TREE):
+        raise ValueError(f"unknown bridging rule {connect!r}; components are joined by 'pairs' (the nearest pair of "
+                         "every two components; True means this) or 'tree' (the minimum spanning tree of those pairs)")
+    return name
+
+
+def _prepared_rows(data, metric, device, who):
+    """The dense float32 rows on the GPU that the searches of ``_neighbor_lists`` run on under ``metric`` (a canonical
+    name, not Manhattan): the translated copy for Euclidean data far from the origin, unit rows for cosine and
+    correlation; a sparse matrix is densified (``ValueError`` when the dense copy does not fit)."""
+    if _sparse.is_sparse(data):
+        csr = _sparse.to_device_csr(data, device)
+        if metric == _metrics.COSINE:
+            csr = _metrics.normalized_csr(csr)
+        if not _densify_sparse_knn(csr.n, csr.n_features, csr.nnz, csr.device):
+            raise ValueError(f"{who} densifies sparse data, and the dense copy of this {csr.n} x {csr.n_features} "
+                             "matrix does not fit in the device memory allowed for it")
+        rows = csr.to_dense()
+        if metric == _metrics.CORRELATION:
+            rows = _metrics.normalized_rows(rows, metric)
+    else:
+        if not isinstance(data, torch.Tensor):
+            data = torch.as_tensor(data)
+        if data.dim() != 2:
+            raise ValueError(f"`data` must be a matrix [n, n_features] (got shape {tuple(data.shape)})")
+        if device is None:
+            device = data.device if data.is_cuda else util.get_default_device()
+        device = util.require_cuda_device(device)
+        rows = data.to(device=device, dtype=torch.float32).contiguous()
+        if metric != _metrics.EUCLIDEAN:
+            rows = _metrics.normalized_rows(rows, metric)
+    if metric == _metrics.EUCLIDEAN:
+        rows, _ = _metrics.translated_rows(rows)
+    return rows
+
+
+def _group_nearest_table(rows, labels, groups, slices=0):
+    """``(d2 float32 [groups, groups], row int32 [groups, groups])`` of ``mde_group_nearest`` for prepared dense
+    float32 ``rows`` and int32 ``labels`` on the same GPU.  The C entry does not check the labels (they live on the
+    device): one reduction here does, and a label outside ``[0, groups)`` is a ``ValueError``."""
+    n, nf = int(rows.shape[0]), int(rows.shape[1])
+    device = rows.device
+    if labels.dim() != 1 or int(labels.shape[0]) != n:
+        raise ValueError(f"`labels` must hold one label per row: {n} rows, labels of shape {tuple(labels.shape)}")
+    labels = labels.to(device=device, dtype=torch.int32).contiguous()
+    lo, hi = (int(v) for v in torch.aminmax(labels)) if n else (0, 0)
+    if lo < 0 or hi >= int(groups):
+        raise ValueError(f"`labels` must lie in [0, groups) = [0, {int(groups)}); it holds {lo if lo < 0 else hi}")
+    lib = _lib.load()
+    d2 = torch.empty((groups, groups), dtype=torch.float32, device=device)
+    row = torch.empty((groups, groups), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        nbytes = int(lib.mde_group_nearest_work_bytes(n, groups, slices))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.mde_group_nearest(n, nf, _lib.ptr(rows), _lib.ptr(labels), groups, slices, _lib.ptr(d2),
+                                         _lib.ptr(row), _lib.ptr(work), _lib.stream_ptr(device)))
+    return d2, row
+
+
+def nearest_between_groups(data, labels, *, metric="euclidean", device=None, slices=0):
+    """For a data matrix and a group label per row, the nearest pair of rows between every two groups
+    (``mde_group_nearest``): a ``GroupNearest(groups, distance, row)``.  With one label per row --
+    classes, clusters, the components of a neighbour graph -- ``distance`` is the single-linkage distance matrix
+    between the groups, and ``(row[A, B], row[B, A])`` the pair that realises it.
+
+    ``labels``: any integers, one per row; they are compacted (``torch.unique``) and ``groups`` lists them in
+    ascending order.  ``distance`` is in the metric's own units, as ``neighbor_graph`` reports lengths, and a pair's
+    value has the bits the k-NN searches give that pair; ties go to the smaller row of the group with the smaller
+    label, then to the smaller row of the other.  ``data`` is prepared as the searches prepare it: rows minus their
+    column means for Euclidean data far from the origin, unit rows for cosine and correlation; a sparse matrix is
+    densified (``ValueError`` if the dense copy does not fit).  The walk forms no distance inside a group and each
+    pair of groups once.  ``slices``: the candidate split of the walk, 0 = automatic; the result does not depend on
+    it.  ``ValueError`` under ``"manhattan"`` (the L1 tile has no such walk), for a ``Graph``, for labels of the
+    wrong length or type, for a single group and for more than 1024."""
+    metric = _metrics.resolve(metric)
+    if metric == _metrics.MANHATTAN:
+        raise ValueError(_NO_MANHATTAN_WALK)
+    if _is_graph(data):
+        raise ValueError("nearest_between_groups measures between the rows of a data matrix; a Graph has no rows")
+    if not isinstance(labels, torch.Tensor):
+        import numpy as np
+        labels = torch.as_tensor(np.asarray(labels))
+    labels = labels.detach().reshape(-1)
+    if labels.dtype == torch.bool or labels.is_floating_point() or labels.is_complex():
+        raise ValueError(f"`labels` must be integers, got dtype {labels.dtype}")
+    if not hasattr(data, "shape") or len(data.shape) != 2:
+        raise ValueError("`data` must be a matrix [n, n_features]")
+    n = int(data.shape[0])
+    if int(labels.shape[0]) != n:
+        raise ValueError(f"`labels` must hold one label per row: `data` has {n} rows and `labels` {int(labels.shape[0])}")
+    rows = _prepared_rows(data, metric, device, "nearest_between_groups")
+    groups, compact = torch.unique(labels.to(rows.device), sorted=True, return_inverse=True)
+    g = int(groups.shape[0])
+    if g < 2:
+        raise ValueError("nearest_between_groups needs at least two groups; `labels` holds one distinct value")
+    if g > MAX_GROUPS:
+        raise ValueError(f"nearest_between_groups serves at most {MAX_GROUPS} groups; `labels` holds {g} distinct "
+                         "values")
+    d2, row = _group_nearest_table(rows, compact, g, int(slices))
+    root, scale = (True, 1.0) if metric == _metrics.EUCLIDEAN else (False, 0.5)
+    distance = (d2.clamp_min(0.0).sqrt() if root else d2) * scale
+    distance.fill_diagonal_(float("inf"))
+    return GroupNearest(groups, distance, row.to(torch.int64))
+
+
+def _spanning_tree_pairs(d2, row):
+    """The ``g - 1`` pairs ``(A, B)``, ``A < B``, of the minimum spanning tree of the complete graph on the groups
+    under the key ``(d2[A, B], row[A, B], row[B, A])`` (Kruskal on the host: at most 1024 groups).  Keys are distinct
+    (no two pairs of groups share a pair of rows), so the tree is unique."""
+    import numpy as np
+    d2, row = d2.cpu().numpy(), row.cpu().numpy()
+    g = d2.shape[0]
+    A, B = np.triu_indices(g, 1)
+    order = np.lexsort((row[B, A], row[A, B], d2[A, B]))
+    parent = list(range(g))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    chosen = []
+    for e in order:
+        ra, rb = find(int(A[e])), find(int(B[e]))
+        if ra != rb:
+            parent[ra] = rb
+            chosen.append((int(A[e]), int(B[e])))
+            if len(chosen) == g - 1:
+                break
+    return chosen
+
+
+def connect_components(data, graph, *, bridges="pairs", metric="euclidean", device=None, slices=0):
+    """Join the connected components of ``graph`` -- a graph on the rows of ``data``, usually their neighbour graph
+    -- by bridges between nearest rows: a ``Connection(graph, bridges, lengths, labels, n_components)``.
+
+    The components come from ``graph.connected_components``; with one component the input graph object itself is
+    returned, with no bridge, and nothing else runs.  Otherwise ``nearest_between_groups`` finds the nearest pair of
+    rows of every two components under ``metric``, and ``bridges="pairs"`` (the default) adds all ``c (c - 1) / 2``
+    of them, the rule of ``sklearn.manifold.Isomap``; ``"tree"`` adds the ``c - 1`` pairs of the minimum spanning
+    tree of the components under the key ``(distance, row, row)``.  Under ``"tree"`` a geodesic between two
+    components may run through a third and overstate their distance; ``"pairs"`` bounds every inter-component
+    distance by a direct bridge.  The new ``Graph`` holds the old edges with their old values, bit for
+    bit, and the bridges with their lengths in the metric's units.  ``ValueError`` when ``data`` and ``graph``
+    disagree on the number of rows, under ``"manhattan"``, and for more than 1024 components (use a larger
+    ``n_neighbors``)."""
+    from pymde_amd import graph as _graph
+    rule = resolve_connect(bridges)
+    metric = _metrics.resolve(metric)
+    if metric == _metrics.MANHATTAN:
+        raise ValueError(_NO_MANHATTAN_WALK)
+    if not isinstance(graph, _graph.Graph):
+        raise ValueError("`graph` must be a pymde_amd.Graph instance.")
+    if _is_graph(data) or not hasattr(data, "shape"):
+        raise ValueError("`data` must be the data matrix whose rows are the nodes of `graph`")
+    n = int(graph.n_items)
+    if int(data.shape[0]) != n:
+        raise ValueError(f"`data` has {int(data.shape[0])} rows and `graph` has {n} nodes; they must agree")
+    count, labels = _graph.connected_components(graph)
+    dev = labels.device
+    if count == 1:
+        return Connection(graph, torch.empty((0, 2), dtype=torch.int64, device=dev),
+                          torch.empty(0, dtype=torch.float32, device=dev), labels, 1)
+    if count > MAX_GROUPS:
+        raise ValueError(f"the graph has {count} connected components and at most {MAX_GROUPS} can be joined; a "
+                         "larger n_neighbors gives fewer components")
+    rows = _prepared_rows(data, metric, dev if device is None else device, "connect_components")
+    d2, row = _group_nearest_table(rows, labels, count, int(slices))
+    if rule == PAIRS:
+        A, B = torch.triu_indices(count, count, 1, device=dev)
+    else:
+        A, B = torch.as_tensor(_spanning_tree_pairs(d2, row), dtype=torch.int64, device=dev).T
+    a, b, value = row[A, B].to(torch.int64), row[B, A].to(torch.int64), d2[A, B]
+    root, scale = (True, 1.0) if metric == _metrics.EUCLIDEAN else (False, 0.5)
+    lengths = (value.clamp_min(0.0).sqrt() if root else value) * scale
+    key, order = torch.sort(torch.minimum(a, b) * n + torch.maximum(a, b))
+    lengths = lengths[order].contiguous()
+    new_edges = torch.stack([key // n, key % n], dim=1).contiguous()
+    # a bridge joins two components, so it is no edge of the graph: the merge is a sort of distinct keys
+    old = graph.edges.to(dev)
+    merged, where = torch.sort(torch.cat([old[:, 0] * n + old[:, 1], key]))
+    values = torch.cat([graph.distances.to(dev), lengths])[where].contiguous()
+    edges = torch.stack([merged // n, merged % n], dim=1).contiguous()
+    return Connection(_graph.Graph._from_unique_edges(edges, values, n), new_edges, lengths, labels, count)
 
 
 def _neighbor_lists(data, k, max_distance=None, device=None, graph_distances=True, approximate=False,

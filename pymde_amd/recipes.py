@@ -239,7 +239,7 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
 
 def preserve_geodesics(data, embedding_dim=2, n_neighbors=15, landmarks=None, *, loss=losses.Quadratic,
                        landmark_selection="farthest", init=None, metric="euclidean", seed=None, device=None,
-                       verbose=False, **search):
+                       verbose=False, connect=False, **search):
     """Preserve the geodesic distances of the data: landmark MDS under the shortest-path metric of a neighbour graph
     (Landmark Isomap, de Silva and Tenenbaum); returns the ``dense.LandmarkMDE`` of ``LandmarkMDE.from_graph``.
 
@@ -249,15 +249,27 @@ def preserve_geodesics(data, embedding_dim=2, n_neighbors=15, landmarks=None, *,
     default, or ``"uniform"``).  ``init``: ``"random"``, ``"classical"``, or ``None``: classical when every (node,
     landmark) pair is joined by a path, random otherwise (one logged line says why).  The cost is one shortest-path
     solve from the landmarks, O(n m) memory; a graph of several components is embedded with the pairs across
-    components left out, so their relative position is arbitrary."""
+    components left out, unless ``connect=`` joins the components first.
+
+    ``connect`` (data matrices only; default False: nothing changes): ``True`` or ``"pairs"`` joins every two
+    connected components of the neighbour graph by their nearest pair of rows, ``"tree"`` by the minimum spanning
+    tree of those pairs (``preprocess.connect_components``, kept on the returned problem as ``mde.connection``).  No
+    pair is missing then, the components are placed relative to each other, and ``init=None`` resolves to
+    ``"classical"``.  With a ``Graph`` as ``data`` it is a ``ValueError`` -- there are no rows to measure between the
+    components; ``graph.connected_components`` is what such a caller can use."""
     if init is not None:
         _dense.check_init(init)
+    rule = preprocess.resolve_connect(connect) if connect else None
+    connection = None
     landmark_selection = _landmarks.resolve_selection(landmark_selection)
     if landmark_selection == _landmarks.KMEANSPP:
         raise ValueError("landmark_selection='kmeans++' has no graph form; the selections here are 'farthest' and "
                          "'uniform'")
     if isinstance(data, _graph.Graph):
         _metrics.check_graph(_metrics.resolve(metric))
+        if rule is not None:
+            raise ValueError("connect= measures between the rows of a data matrix, and a Graph has none; "
+                             "graph.connected_components reports the components of a Graph")
         graph = data
     else:
         if not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
@@ -268,13 +280,22 @@ def preserve_geodesics(data, embedding_dim=2, n_neighbors=15, landmarks=None, *,
         if verbose:
             problem.LOGGER.info(f"Building the {n_neighbors}-nearest-neighbour graph of {n_items} rows")
         graph = preprocess.neighbor_graph(data, n_neighbors, metric=metric, device=device, verbose=verbose, **search)
+        if rule is not None:
+            connection = preprocess.connect_components(data, graph, bridges=rule, metric=metric, device=device)
+            graph = connection.graph
+            if verbose:
+                problem.LOGGER.info(f"The neighbour graph has {connection.n_components} connected component(s); "
+                                    f"joined by {int(connection.bridges.shape[0])} bridge(s) ('{rule}')")
     if landmarks is None:
         landmarks = min(1000, graph.n_items // 2)
     if verbose:
         problem.LOGGER.info(f"Shortest paths from {landmarks} landmarks ({landmark_selection}) to "
                             f"{graph.n_items} nodes")
-    return _dense.LandmarkMDE._build_from_graph(graph, landmarks, embedding_dim, loss, None, seed,
-                                                landmark_selection, init, None, None)
+    mde = _dense.LandmarkMDE._build_from_graph(graph, landmarks, embedding_dim, loss, None, seed,
+                                               landmark_selection, init, None, None)
+    if connection is not None:
+        mde.connection = connection
+    return mde
 
 
 def _preserve_distances_dense(data, embedding_dim, loss, constraint, device, verbose, metric, weights=None,
