@@ -648,6 +648,43 @@ int mde_rows_normalize(int64_t n, int32_t nf, const float* data, int32_t center,
  * distance is undefined (a zero row under cosine, a constant row under correlation). */
 int mde_pair_distances_metric(int64_t n, int32_t nf, const float* data, int64_t p, const int64_t* edges,
                               int32_t metric, float* out, void* stream);
+/* Bit-packed binary data (csrc/mde_bits.hip).  A matrix of n rows and nf 0/1 features,
+ * 1 <= nf < 2^24, is words int32 [n, nw], nw = ceil(nf / 32), row-major on the device: feature f is bit f & 31 of
+ * word f >> 5 and every padding bit is zero; counts int32 [n] are the row popcounts.  With a, b the counts of two
+ * rows and t the popcount of the AND of their words, a pair's distance is one correctly rounded float32 quotient
+ * of exact integers, the definitions of scipy.spatial.distance:
+ *   kind 0  Jaccard  (a + b - 2 t) / (a + b - t), 0 when a + b - t == 0 (two empty rows)
+ *   kind 1  Hamming  (a + b - 2 t) / nf
+ * so a pair has the same bits in every function below and for every slice count.
+ * mde_bits_pack: data float32 [n, nf] -> words and counts (one wave per row, a 64-lane ballot of x != 0 is two
+ * words).  bad_row int32 [1] on the device = the first row that holds a value other than 0 or 1, NaN included
+ * (INT32_MAX when there is none; the words of such a row mean nothing).
+ * mde_bits_pack_csr: the same from CSR (indptr int64 [n + 1], indices int32 [nnz], values float32 [nnz]): the
+ * stored values are what is checked, a stored 0 sets nothing, a duplicate entry sets its bit once (integer
+ * atomic OR into zeroed words; the counts are taken from the words), and a column outside [0, nf) makes the row
+ * bad.  Arguments are checked on the host before any launch: MDE_E_INVALID with a message.  ASYNC. */
+int mde_bits_pack(int64_t n, int32_t nf, const float* data, int32_t* words, int32_t* counts, int32_t* bad_row,
+                  void* stream);
+int mde_bits_pack_csr(int64_t n, int32_t nf, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                      const float* values, int32_t* words, int32_t* counts, int32_t* bad_row, void* stream);
+/* Exact k nearest rows of C [n_c, nw] for every row of Q [n_q, nw] under `kind`, the contract of mde_knn_cross:
+ * idx_out [n_q, k] int32 (-1 in the slots beyond the rows available), dist_out [n_q, k] float32 distances (not
+ * squares), each row ordered by (value, index); 1 <= k <= 64; n_q, n_c < 2^31; nw == ceil(nf / 32).
+ * self != 0: Q == C, q_counts == c_counts and n_q == n_c (the self-join); only the pair of a row with itself is
+ * excluded, so duplicate rows list each other at 0.  slices as in mde_knn_cross (grid (query block of 64 rows,
+ * corpus slice); 0: automatic; the per-slice lists are folded by (value, index)): the result is bit-identical for
+ * every slice count and on every run.  No floating-point atomics.
+ * work: mde_bits_knn_work_bytes(n_q, n_c, k, slices) bytes of scratch (the per-slice lists; 8 bytes with one
+ * slice); the call allocates nothing.  Arguments are checked on the host before any launch: MDE_E_INVALID with
+ * a message.  ASYNC. */
+int64_t mde_bits_knn_work_bytes(int64_t n_q, int64_t n_c, int32_t k, int32_t slices);
+int mde_bits_knn(int64_t n_q, int64_t n_c, int32_t nw, int32_t nf, const int32_t* Q, const int32_t* q_counts,
+                 const int32_t* C, const int32_t* c_counts, int32_t self, int32_t kind, int32_t k, int32_t slices,
+                 int32_t* idx_out, float* dist_out, void* work, void* stream);
+/* out[e] = the distance under `kind` between rows i and j of the packed matrix for every edge (i, j) of edges
+ * [p, 2] (int64), with the bits mde_bits_knn gives the pair.  NaN for an endpoint outside [0, n). */
+int mde_bits_pair_distances(int64_t n, int32_t nw, int32_t nf, const int32_t* words, const int32_t* counts, int64_t p,
+                            const int64_t* edges, int32_t kind, float* out, void* stream);
 /* Approximate k-NN by an inverted file (csrc/mde_ann.hip) [ref: preprocess/data_matrix.py:125-143].
  * Query-against-base search restricted to block-sparse (query tile, candidate range) pairs.  Query
  * position p reads row q_map[p] of Q [n_q, nf] (q_map NULL: row p), base position c reads row b_map[c] of

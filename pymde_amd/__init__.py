@@ -18,6 +18,8 @@ from pymde_amd import quadratic  # noqa: F401
 from pymde_amd import preprocess  # noqa: F401
 from pymde_amd import quality  # noqa: F401
 from pymde_amd import affinity  # noqa: F401
+from pymde_amd import binary  # noqa: F401
+from pymde_amd.binary import BitMatrix  # noqa: F401
 from pymde_amd import landmarks  # noqa: F401
 from pymde_amd import classical  # noqa: F401
 from pymde_amd import isotonic  # noqa: F401

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libmde_hip.so")
 SOURCES = ["mde_plan.hip", "mde_distortion.hip", "mde_fused_small.hip", "mde_fused_wide.hip", "mde_edge_eval.hip", "mde_ring.hip", "mde_ring_build.hip", "mde_ring_params.hip", "mde_ring_check.hip", "mde_ring_hub.hip", "mde_ring_k_log1p.hip", "mde_ring_k_pushpull.hip",
-           "mde_ring_k_penalty.hip", "mde_ring_k_penalty2.hip", "mde_ring_k_loss.hip", "mde_ring_k_loss2.hip", "mde_ring_k_runtime.hip", "mde_vec.hip", "mde_std.hip", "mde_lbfgs.hip", "mde_turn.hip", "mde_mfma.hip", "mde_edges.hip", "mde_knn.hip", "mde_knn_bf16.hip", "mde_knn_rank.hip", "mde_pair_moments.hip", "mde_matrix_quality.hip", "mde_pair_loss.hip", "mde_pair_apply.hip", "mde_rows.hip", "mde_metric.hip", "mde_ann.hip", "mde_ann_refine.hip", "mde_sparse.hip", "mde_spmm.hip", "mde_graph.hip", "mde_graph_sssp.hip", "mde_graph_components.hip", "mde_group_nearest.hip",
+           "mde_ring_k_penalty.hip", "mde_ring_k_penalty2.hip", "mde_ring_k_loss.hip", "mde_ring_k_loss2.hip", "mde_ring_k_runtime.hip", "mde_vec.hip", "mde_std.hip", "mde_lbfgs.hip", "mde_turn.hip", "mde_mfma.hip", "mde_edges.hip", "mde_knn.hip", "mde_knn_bf16.hip", "mde_knn_rank.hip", "mde_pair_moments.hip", "mde_matrix_quality.hip", "mde_pair_loss.hip", "mde_pair_apply.hip", "mde_rows.hip", "mde_metric.hip", "mde_bits.hip", "mde_ann.hip", "mde_ann_refine.hip", "mde_sparse.hip", "mde_spmm.hip", "mde_graph.hip", "mde_graph_sssp.hip", "mde_graph_components.hip", "mde_group_nearest.hip",
            "mde_landmarks.hip", "mde_affinity.hip", "mde_isotonic.hip"]
 ARCH = "gfx950"
 

@@ -137,6 +137,12 @@ SYMBOLS = {
     "mde_knn_l1":(c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mde_rows_normalize": (c_i32, [c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mde_pair_distances_metric": (c_i32, [c_i64, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "mde_bits_pack": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_bits_pack_csr": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mde_bits_knn_work_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "mde_bits_knn": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp,
+                             c_vp, c_vp, c_vp]),
+    "mde_bits_pair_distances": (c_i32, [c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "mde_sparse_rows_normalize": (c_i32, [c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mde_knn_pairs": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
     "mde_knn_calibrate": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_i32, ctypes.c_double, c_i32, c_f32, c_i32,

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from pymde_amd import _lib
+from pymde_amd import binary as _binary
 from pymde_amd import classical as _classical
 from pymde_amd import constraints
 from pymde_amd import graph as _graph
@@ -185,6 +186,8 @@ def loss_spec(loss):
 def check_source(data, metric):
     """Canonical name of a metric the Gram tile serves; ``ValueError`` for Manhattan and for a ``Graph`` (no device is
     needed to say so)."""
+    _binary.refuse(data, "a dense problem (DenseMDE, DensePlacement, LandmarkMDE, dense=True, landmarks=, "
+                         "classical_mds(data=...))", "pass the distances themselves as distance_matrix=")
     metric = _metrics.resolve(metric)
     if preprocess._is_graph(data):
         raise ValueError("a dense problem forms its deviations from the rows of a data matrix; for a Graph pass its "

@@ -18,6 +18,7 @@ import collections
 import torch
 
 from pymde_amd import _lib, util
+from pymde_amd import binary as _binary
 from pymde_amd import graph as _graph
 from pymde_amd import metrics as _metrics
 from pymde_amd import preprocess as _preprocess
@@ -57,6 +58,7 @@ def resolve_selection(selection):
 
 
 def _check_source(data, metric):
+    _binary.refuse(data, "landmarks.select")
     metric = _metrics.resolve(metric)
     if _preprocess._is_graph(data):
         raise ValueError("landmarks are selected among the rows of a data matrix; a Graph has no rows (the metrics "

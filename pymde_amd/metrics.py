@@ -29,7 +29,8 @@ def resolve(metric):
     name = ALIASES.get(name, name) if isinstance(name, str) else name
     if name not in METRICS:
         raise ValueError(f"unknown metric {metric!r}; the metrics are {', '.join(METRICS)} "
-                         f"(aliases: {', '.join(sorted(ALIASES))})")
+                         f"(aliases: {', '.join(sorted(ALIASES))}); binary data under the Jaccard or Hamming "
+                         "distance enter as a BitMatrix, pymde_amd.binary.pack(data)")
     return name
 
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from pymde_amd import _lib
+from pymde_amd import binary as _binary
 from pymde_amd import metrics as _metrics
 from pymde_amd import sparse as _sparse
 from pymde_amd import util
@@ -118,6 +119,7 @@ def principal_components(data, n_components, *, n_oversamples=10, n_iter=4, seed
     iterations bring the leading singular values within about 1e-6 of the exact ones when the spectrum has a gap
     after ``n_components``; without a gap the subspace is one that captures as much variance, not the
     eigenvectors themselves.  ``util.SolverError`` when a block loses rank (data of rank below ``r``)."""
+    _binary.refuse(data, "principal_components")
     is_sparse = _sparse.is_sparse(data)
     if not is_sparse and not isinstance(data, torch.Tensor):
         data = torch.as_tensor(data)

@@ -17,6 +17,7 @@ import torch
 
 from pymde_amd import _lib
 from pymde_amd import ann as _ann
+from pymde_amd import binary as _binary
 from pymde_amd import metrics as _metrics
 from pymde_amd import sparse as _sparse
 from pymde_amd import util
@@ -249,7 +250,13 @@ def k_nearest_neighbors(data, k, max_distance=None, device=None, graph_distances
     the float32 search takes.  Data whose neighbours differ by less than bfloat16 resolves -- points on a
     line, say -- lose recall.  A sparse matrix is served when it is densified; one that would stay on the
     sparse kernel is an error.  ``verbose=True`` logs a recall@k estimated on 1 000 sampled rows against the
-    float32 search."""
+    float32 search.
+
+    A ``BitMatrix`` (``pymde_amd.binary.pack``: bit-packed binary data) is searched exactly under its own Jaccard
+    or Hamming distance by ``mde_bits_knn``; ``max_distance`` is in that distance's units.
+    ``metric``, ``precision``, ``n_candidates``, ``approximate`` and ``n_refine`` stay at their defaults beside it (a
+    ``ValueError`` otherwise); ``n_lists``, ``n_probe``, ``seed``, ``verbose`` and ``graph_distances`` have no effect
+    on it."""
     idx, values, bound, _, _ = _neighbor_lists(data, k, max_distance, device, graph_distances, approximate, n_lists,
                                                n_probe, seed, verbose, metric, precision, n_candidates, n_refine)
     return _neighbor_lists_to_graph(idx.shape[0], idx.shape[1], idx, values, bound, idx.device)
@@ -269,6 +276,7 @@ def neighbor_graph(data, k, *, metric="euclidean", max_distance=None, connect=Fa
     if _is_graph(data):
         raise ValueError("neighbor_graph takes a data matrix; a Graph is already a graph")
     if connect:
+        _binary.refuse(data, "neighbor_graph(connect=...)")
         rule = resolve_connect(connect)
         if _metrics.resolve(metric) == _metrics.MANHATTAN:
             raise ValueError(_NO_MANHATTAN_WALK)
@@ -392,6 +400,7 @@ def nearest_between_groups(data, labels, *, metric="euclidean", device=None, sli
     pair of groups once.  ``slices``: the candidate split of the walk, 0 = automatic; the result does not depend on
     it.  ``ValueError`` under ``"manhattan"`` (the L1 tile has no such walk), for a ``Graph``, for labels of the
     wrong length or type, for a single group and for more than 1024."""
+    _binary.refuse(data, "nearest_between_groups")
     metric = _metrics.resolve(metric)
     if metric == _metrics.MANHATTAN:
         raise ValueError(_NO_MANHATTAN_WALK)
@@ -467,6 +476,7 @@ def connect_components(data, graph, *, bridges="pairs", metric="euclidean", devi
     ``n_neighbors``)."""
     from pymde_amd import graph as _graph
     rule = resolve_connect(bridges)
+    _binary.refuse(data, "connect_components")
     metric = _metrics.resolve(metric)
     if metric == _metrics.MANHATTAN:
         raise ValueError(_NO_MANHATTAN_WALK)
@@ -515,6 +525,9 @@ def _neighbor_lists(data, k, max_distance=None, device=None, graph_distances=Tru
     distance of an entry is ``scale * (sqrt(values) if root else values)``: ``(True, 1.0)`` for the Euclidean
     searches, which rank by the squared distance, ``(False, 0.5)`` for cosine and correlation (the squared
     chord of the unit rows), ``(False, 1.0)`` for Manhattan and for a ``Graph``."""
+    if _binary.is_bits(data):
+        return _bits_neighbor_lists(data, k, max_distance, device, approximate, metric, precision, n_candidates,
+                                    n_refine)
     metric = _metrics.resolve(metric)
     _metrics.check_approximate(metric, approximate)
     precision = _check_precision_arguments(precision, n_candidates, k, metric, approximate, _is_graph(data))
@@ -570,6 +583,32 @@ def _neighbor_lists(data, k, max_distance=None, device=None, graph_distances=Tru
                                    n_refine)
     max_d2 = None if max_distance is None else float(max_distance) ** 2
     return idx, d2, max_d2, True, 1.0
+
+
+def _check_bits_search(metric, approximate, precision, n_candidates, n_refine=0):
+    """The argument errors of a search on a ``BitMatrix`` (they need no device): ``metric=`` at its default, no
+    approximate search, no bfloat16 shortlist."""
+    _binary.check_metric(metric)
+    if approximate or n_refine:
+        raise ValueError("approximate=True applies to float data matrices; a BitMatrix has no approximate search "
+                         "(the inverted file's k-means lists are Euclidean)")
+    if resolve_precision(precision) != FLOAT32 or n_candidates is not None:
+        raise ValueError("precision='bfloat16' and n_candidates apply to float data matrices; a BitMatrix is "
+                         "searched exactly, in integers")
+
+
+def _bits_neighbor_lists(bits, k, max_distance, device, approximate, metric, precision, n_candidates, n_refine):
+    """``_neighbor_lists`` of a ``BitMatrix``: the exact self-join of ``mde_bits_knn`` under the matrix's own
+    distance; the values are the distances themselves (``root=False, scale=1.0``).  ``approximate``, ``n_refine``,
+    a ``precision`` other than float32 and ``n_candidates`` are refused; the knobs that only steer those searches
+    or a ``Graph`` -- ``n_lists``, ``n_probe``, ``seed``, ``verbose``, ``graph_distances`` -- have no effect here,
+    as ``n_lists`` / ``n_probe`` have none on float data without ``approximate=True``."""
+    _check_bits_search(metric, approximate, precision, n_candidates, n_refine)
+    if device is not None:
+        bits = bits.to(util.require_cuda_device(device))
+    k = _clamp_k(k, bits.shape[0])
+    idx, dist = _binary.knn_lists(bits, bits, k, self_join=True)
+    return idx, dist, None if max_distance is None else float(max_distance), False, 1.0
 
 
 _BF16_SPARSE_DOES_NOT_FIT = (
@@ -827,7 +866,13 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
     ``precision="bfloat16"`` and ``n_candidates`` as in ``k_nearest_neighbors``: a bfloat16 shortlist of
     ``n_candidates`` rows of ``data`` per query (default ``min(64, max(2 k, k + 16))``, at most the rows of
     ``data``), re-ranked with the float32 distances of the float32 search; the bfloat16 copies of both
-    matrices are centred at the column means of ``data``."""
+    matrices are centred at the column means of ``data``.
+
+    Two ``BitMatrix`` arguments of equal ``n_features`` and ``distance`` are searched by ``mde_bits_knn`` under
+    that distance (the other keywords at their defaults); one ``BitMatrix`` beside a float matrix is a
+    ``ValueError``."""
+    if _binary.is_bits(queries) or _binary.is_bits(data):
+        return _bits_cross_nearest_neighbors(queries, data, k, max_distance, metric, device, precision, n_candidates)
     metric = _metrics.resolve(metric)
     precision = _check_precision_arguments(precision, n_candidates, k, metric,
                                            graph=_is_graph(queries) or _is_graph(data))
@@ -877,6 +922,31 @@ def cross_nearest_neighbors(queries, data, k, max_distance=None, metric="euclide
     else:
         idx32, d2 = _cross_knn_lists(Q, C, k)
     dist = d2.sqrt() if metric == _metrics.EUCLIDEAN else 0.5 * d2
+    empty = idx32 < 0
+    if max_distance is not None:
+        empty = empty | ~(dist <= float(max_distance))
+    idx = idx32.to(torch.int64)
+    idx[empty] = -1
+    dist[empty] = float("inf")
+    return idx, dist
+
+
+def _bits_cross_nearest_neighbors(queries, data, k, max_distance, metric, device, precision, n_candidates):
+    """``cross_nearest_neighbors`` of two ``BitMatrix`` arguments (equal ``n_features`` and ``distance``)."""
+    _check_bits_search(metric, False, precision, n_candidates)
+    _binary.check_pair(queries, data)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    n_q, n_c = queries.shape[0], data.shape[0]
+    if n_c < 1:
+        raise ValueError("`data` needs at least one row")
+    device = util.require_cuda_device(data.device if device is None else device)
+    queries, data = queries.to(device), data.to(device)
+    if n_q == 0:
+        return (torch.empty((0, k), dtype=torch.int64, device=device),
+                torch.empty((0, k), dtype=torch.float32, device=device))
+    idx32, dist = _binary.knn_lists(queries, data, k)
     empty = idx32 < 0
     if max_distance is not None:
         empty = empty | ~(dist <= float(max_distance))

@@ -24,6 +24,7 @@ import torch
 
 from pymde_amd import _lib
 from pymde_amd import average_distortion as _ad
+from pymde_amd import binary as _binary
 from pymde_amd import sparse as _sparse
 from pymde_amd import util
 from pymde_amd.functions import penalties
@@ -244,6 +245,7 @@ def pca(Y, embedding_dim, device=None):
     ``scores * sqrt(n) / singular_values`` of ``preprocess.principal_components`` (the randomized
     route on the centred matrix, with its defaults) are returned, and ``embedding_dim`` must then be
     below ``min(n, k)``."""
+    _binary.refuse(Y, "pca")
     if _sparse.is_sparse(Y):
         from pymde_amd.pca import principal_components
         pc = principal_components(Y, embedding_dim, device=device)

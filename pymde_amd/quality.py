@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from pymde_amd import _lib, util
+from pymde_amd import binary as _binary
 from pymde_amd import metrics as _metrics
 from pymde_amd import preprocess as _preprocess
 
@@ -40,6 +41,8 @@ _RANKED_METRICS = (_metrics.EUCLIDEAN, _metrics.COSINE, _metrics.CORRELATION)
 def _resolve_metric(metric, *matrices):
     """Canonical name of a metric the rank kernel serves; ``ValueError`` otherwise, and for a ``Graph``
     (no device is needed to say so)."""
+    for m in matrices:
+        _binary.refuse(m, "pymde_amd.quality", "the matrix_* scores take the distances themselves")
     metric = _metrics.resolve(metric)
     if metric not in _RANKED_METRICS:
         raise ValueError(f"metric={metric!r} has no rank kernel; the metrics pymde_amd.quality supports are "

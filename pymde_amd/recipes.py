@@ -13,6 +13,7 @@ import torch
 
 from pymde_amd import _lib
 from pymde_amd import affinity as _affinity
+from pymde_amd import binary as _binary
 from pymde_amd import constraints
 from pymde_amd import dense as _dense
 from pymde_amd import graph as _graph
@@ -54,7 +55,16 @@ def distances(data, retain_fraction=1.0, seed=None, device=None, metric="euclide
     (``mde_pair_distances_metric``), so near-duplicate rows keep their small cosine / correlation
     distances.  Sparse data: cosine scales the rows to unit length and halves the squared sparse distance;
     correlation and Manhattan densify (an error if the dense copy does not fit).  A row without a
-    direction (all zero under cosine, constant under correlation) is an error."""
+    direction (all zero under cosine, constant under correlation) is an error.
+
+    A ``BitMatrix`` (``pymde_amd.binary``) gives its own Jaccard or Hamming distances, with the bits the searches
+    give each pair (``mde_bits_pair_distances``); ``metric`` stays at its default beside it."""
+    if _binary.is_bits(data):
+        _binary.check_metric(metric)
+        if device is not None:
+            data = data.to(util.require_cuda_device(device))
+        edges = _distance_edges(data.shape[0], retain_fraction, seed, data.device)
+        return EdgeGraph(edges, _binary.pair_distances(data, edges), data.shape[0])
     metric = _metrics.resolve(metric)
     if metric != _metrics.EUCLIDEAN:
         return _metric_distances(data, retain_fraction, seed, device, metric)
@@ -208,6 +218,8 @@ def preserve_distances(data, embedding_dim=2, loss=losses.Absolute, constraint=N
     is_graph = isinstance(data, _graph.Graph)
     if is_graph:
         _metrics.check_graph(metric)
+    if _binary.is_bits(data):
+        _binary.check_metric(metric)
     if not is_graph and not isinstance(data, torch.Tensor) and not hasattr(data, "shape"):
         raise ValueError("`data` must be a np.ndarray/torch.Tensor/sparse data matrix, or a pymde_amd.Graph.")
     n_items = data.n_items if is_graph else int(data.shape[0])
@@ -257,6 +269,7 @@ def preserve_geodesics(data, embedding_dim=2, n_neighbors=15, landmarks=None, *,
     pair is missing then, the components are placed relative to each other, and ``init=None`` resolves to
     ``"classical"``.  With a ``Graph`` as ``data`` it is a ``ValueError`` -- there are no rows to measure between the
     components; ``graph.connected_components`` is what such a caller can use."""
+    _binary.refuse(data, "preserve_geodesics")
     if init is not None:
         _dense.check_init(init)
     rule = preprocess.resolve_connect(connect) if connect else None
@@ -366,6 +379,11 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     balance against the -1 repulsive edges.  The factor is taken before any ``Anchored`` edge removal.  The
     ``affinity.Calibration`` is kept on the returned problem as ``mde.neighbor_calibration``."""
     affinity_spec = _affinity.parse_weights(weights)
+    if _binary.is_bits(data):
+        # its own distance, one exact search: the argument errors, before any device is required
+        preprocess._check_bits_search(metric, approximate_neighbors not in (None, False), neighbor_precision, None)
+        if n_components is not None:
+            raise ValueError("n_components applies to float data matrices; a BitMatrix has no principal components")
     metric = _metrics.resolve(metric)
     is_graph = isinstance(data, _graph.Graph)
     if n_components is not None:
@@ -385,11 +403,14 @@ def preserve_neighbors(data, embedding_dim=2, attractive_penalty=penalties.Log1p
     _metrics.check_approximate(metric, bool(knn_options))
     if is_graph and knn_options:
         raise ValueError("approximate_neighbors applies to data matrices; a Graph has no approximate search")
-    if not is_graph and not isinstance(data, torch.Tensor) and not _sparse.is_sparse(data):
+    is_bits = _binary.is_bits(data)
+    if not is_graph and not is_bits and not isinstance(data, torch.Tensor) and not _sparse.is_sparse(data):
         data = torch.as_tensor(data)
     if device is None:
         if is_graph:
             device = data.edges.device
+        elif is_bits:
+            device = data.device
         else:
             device = data.device if isinstance(data, torch.Tensor) and data.is_cuda else util.get_default_device()
     device = util.require_cuda_device(device)
@@ -564,6 +585,10 @@ def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repu
     coordinate system: with ``pc`` the fitted ``PrincipalComponents`` (``mde.principal_components``, or the
     result of ``preprocess.principal_components(data, 50)``),
         ``extend_embedding(pc.scores, X, pc.transform(new_data))``."""
+    if _binary.is_bits(data) or _binary.is_bits(new_data):
+        # two BitMatrix of one distance and width: the argument errors, before any device is required
+        preprocess._check_bits_search(metric, False, neighbor_precision, None)
+        _binary.check_pair(new_data, data)
     metric = _metrics.resolve(metric)
     neighbor_precision = preprocess.resolve_precision(neighbor_precision)
     if metric == _metrics.MANHATTAN:
@@ -582,6 +607,8 @@ def extend_embedding(data, X, new_data, attractive_penalty=penalties.Log1p, repu
         raise ValueError("`new_data` needs at least one row")
     if device is None:
         on_gpu = [t.device for t in (X, data, new_data) if isinstance(t, torch.Tensor) and t.is_cuda]
+        if _binary.is_bits(data):
+            on_gpu.insert(0, data.device)
         device = on_gpu[0] if on_gpu else util.get_default_device()
     device = util.require_cuda_device(device)
     X = X.detach().to(device=device, dtype=torch.float32).contiguous()
